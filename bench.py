@@ -18,7 +18,13 @@ WORLD_SIZE must equal --gpus.  ``--dry-run`` runs the launcher, rendezvous,
 shard split and the timing/max-over-ranks logic on CPU (gloo) with no GPU
 work (tests/test_bench_launcher.py).
 
-The JSON line carries
+A plain run sets up, settles and warms up, times the --steps steps, writes
+the last step's outputs if ``--dump-outputs DIR`` is given, and prints the
+JSON line with the headline (metric, value, unit, ms_per_step, dtype, config).
+``--full`` then goes on to everything else, each a run of its own after the
+timed steps: the other distribution, the PCIe-inclusive rate, the C2 / C3 /
+C5 config lines, the stage and chain timing, and
+
   roofline     -- the dominant kernel stage, achieved vs MI355X peak
   cpu_baseline -- the CPU oracle (sequential C port of the reference core) +
                   torch fp32 CPU forward, timed on a bounded sample (rank 0, N=1)
@@ -79,6 +85,27 @@ def chain_ideal_s_per_point(F: int, C: int) -> tuple:
     return tuple(sum(2.0 * K * N / peak[kind] for K, N, kind in ch) for ch in chain_layers(F, C))
 
 
+def dump_outputs(dirname: str, out, rank: int, cap_bytes: int = 48 << 20) -> None:
+    """--dump-outputs: the last timed step's return value as float32 .npy files,
+    whole (16 x 1000 x 29 log-probs: 1.9 MB; config C5's three levels: 6.5 MB).
+    ``log_probs.npy``, or ``log_probs_level<i>.npy`` per level with --levels;
+    ranks beyond the first add ``.rank<r>`` before the extension.  Shapes whose
+    outputs exceed ``cap_bytes`` in all are written as a fixed (seed 0) sample of the
+    flattened elements, in index order."""
+    os.makedirs(dirname, exist_ok=True)
+    outs = out if isinstance(out, list) else [out]
+    names = [f"log_probs_level{i}" for i in range(len(outs))] if isinstance(out, list) else ["log_probs"]
+    cap = cap_bytes // 4  # float32 elements in all
+    total = sum(o.numel() for o in outs)
+    for name, o in zip(names, outs):
+        a = o.detach().to(torch.float32).cpu().numpy()
+        if total > cap:
+            keep = np.random.default_rng(0).choice(a.size, size=max(1, a.size * cap // total), replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        tag = f".rank{rank}" if rank else ""
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), a)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -127,6 +154,13 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the other "
+                         "distribution, the PCIe-inclusive rate, the C2 / C3 / C5 config lines, stage and chain "
+                         "timing with the roofline, the CPU baseline (each still has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the log-probs a caller of the timed path "
+                         "receives) as DIR/<name>.npy, float32")
     ap.add_argument("--no-stream-lines", action="store_true",
                     help="skip the C2 / C3 lines over consecutive batches on several streams")
     ap.add_argument("--settle-ms", type=float, default=300.0,
@@ -279,6 +313,69 @@ def main() -> None:
     elapsed = D.max_over_ranks(elapsed)
     total_clouds = world * B * args.steps
     value = total_clouds / elapsed
+    stats = all_run_stats()
+    assert all(s.rc == 0 for s in stats), [s.rc for s in stats]
+    assert all(torch.isfinite(o).all() for o in (out if isinstance(out, list) else [out]))
+    if args.dump_outputs:
+        # the last timed step's return value, before anything below replays the step again
+        dump_outputs(args.dump_outputs, out, rank)
+
+    if rank == 0:
+        line = {
+            "metric": ("clouds/sec NDT preprocess+PointNet fwd, 100k pts->1000 NDs, batch=16" if not levels else
+                       "clouds/sec NDT multiscale {%s} NDs + PointNet fwd per level, 100k pts, batch=16"
+                       % ",".join(map(str, levels))),
+            "value": round(value, 2),
+            "unit": "clouds/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle": {"ms": args.settle_ms, "steps": n_settle},
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
+            "pipeline_front_share": list(getattr(graphed, "front_share", [])) if not args.eager else None,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": (f"f64 NDT; PointNet fp32-accurate split-bf16x3 (6 products) on {11 if pointnet_hip.X6_NARROW else 7}"
+                      " per-point layers, fp32 MFMA on the K=16 first layers and the TNet / seg-bias FC layers"
+                      if pointnet_hip.SPLIT_BF16 else "f64 NDT; PointNet fp32 MFMA"),
+            "data": f"synthetic {args.kind} clouds (SURVEY 8d), random-init weights",
+            "full": args.full,
+            "measurement_notes": [
+                "U clouds reach exactly k occupied voxels at the accepted size, so their level-1 prune removes "
+                "nothing: the run counts the KL events (stats num_events / num_kl) and builds the sorted list only "
+                "on demand (ndnet_ndt_set_lazy_list; bit-equal to the eager build by test_lazy_list_equals_eager). "
+                "The L line (other_distribution, with --full) times the KL scoring, sort and prune of ~121 pruned "
+                "NDs per cloud.",
+                "Every ring slot replays one resident batch (bench inputs already in HBM, as the contract asks; "
+                "the slots' inputs total ~115 MB, within the 256 MB Infinity Cache); pcie_inclusive (with --full) "
+                "streams the batch from pinned host memory instead."] if not levels else None,
+            "config": {"workload": (f"batch {B} x {n} pts -> {k} NDs, NDTNetSegmentation F={F} C={C} eval"
+                                    if not levels and world == 1 else
+                                    f"C4: {B * world} clouds end to end ({n} pts -> {k} NDs -> NDTNetSegmentation "
+                                    f"F={F} C={C} eval), {B} per rank over {world} GPUs, contiguous shards"
+                                    if not levels else
+                                    f"C5: batch {B} x {n} pts -> downsample {levels[0]} -> prune "
+                                    f"{' -> '.join(map(str, levels[1:]))}, NDTNetSegmentation F={F} C={C} eval "
+                                    f"per level"),
+                       "launch": "eager" if args.eager else (
+                           "hip graph per step (ndnet.pipeline.GraphedSegmentation)" if args.no_pipeline
+                           else f"NDT(batch i) || forward(batch i-1): a hip graph per stage and ring slot "
+                                f"({graphed.R} buffers), one NDT stream + {graphed.F} forward streams (step i's "
+                                f"forward on stream i % {graphed.F}) ordered by events only, joined once per timed "
+                                f"region (ndnet.pipeline.PipelinedSegmentation.replay_steps)"),
+                       "global_batch": B * world, "points": n, "nds": k, "parallelism": f"dp{world} (clouds sharded)",
+                       "dist_backend": args.dist_backend if world > 1 else None,
+                       **({"rehearsal": f"{world} ranks on {ndev} GPU(s)"} if world > ndev else {})},
+        }
+    if not args.full:
+        # the plain run ends here: everything below takes runs of its own (--full)
+        if rank == 0:
+            print(json.dumps(line))
+        if dist:
+            torch.distributed.destroy_process_group()
+        return
 
     # ---- the other synthetic distribution on the same graph (SURVEY §8d "also
     # report L"): the L clouds exercise the prune (~128 of ~1128 NDs removed) ----
@@ -779,51 +876,7 @@ def main() -> None:
                                              f"GPU (gpurun: 16 per GPU), not every core of the host"}}
 
     if rank == 0:
-        line = {
-            "metric": ("clouds/sec NDT preprocess+PointNet fwd, 100k pts->1000 NDs, batch=16" if not levels else
-                       "clouds/sec NDT multiscale {%s} NDs + PointNet fwd per level, 100k pts, batch=16"
-                       % ",".join(map(str, levels))),
-            "value": round(value, 2),
-            "unit": "clouds/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle": {"ms": args.settle_ms, "steps": n_settle},
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
-            "pipeline_front_share": list(getattr(graphed, "front_share", [])) if not args.eager else None,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": (f"f64 NDT; PointNet fp32-accurate split-bf16x3 (6 products) on {11 if pointnet_hip.X6_NARROW else 7}"
-                      " per-point layers, fp32 MFMA on the K=16 first layers and the TNet / seg-bias FC layers"
-                      if pointnet_hip.SPLIT_BF16 else "f64 NDT; PointNet fp32 MFMA"),
-            "data": f"synthetic {args.kind} clouds (SURVEY 8d), random-init weights",
-            "measurement_notes": [
-                "U clouds reach exactly k occupied voxels at the accepted size, so their level-1 prune removes "
-                "nothing: the run counts the KL events (stats num_events / num_kl) and builds the sorted list only "
-                "on demand (ndnet_ndt_set_lazy_list; bit-equal to the eager build by test_lazy_list_equals_eager). "
-                "The L line (other_distribution) times the KL scoring, sort and prune of ~121 pruned NDs per cloud.",
-                "Every ring slot replays one resident batch (bench inputs already in HBM, as the contract asks; "
-                "the slots' inputs total ~115 MB, within the 256 MB Infinity Cache); pcie_inclusive streams the "
-                "batch from pinned host memory instead."] if not levels else None,
-            "config": {"workload": (f"batch {B} x {n} pts -> {k} NDs, NDTNetSegmentation F={F} C={C} eval"
-                                    if not levels and world == 1 else
-                                    f"C4: {B * world} clouds end to end ({n} pts -> {k} NDs -> NDTNetSegmentation "
-                                    f"F={F} C={C} eval), {B} per rank over {world} GPUs, contiguous shards"
-                                    if not levels else
-                                    f"C5: batch {B} x {n} pts -> downsample {levels[0]} -> prune "
-                                    f"{' -> '.join(map(str, levels[1:]))}, NDTNetSegmentation F={F} C={C} eval "
-                                    f"per level"),
-                       "launch": "eager" if args.eager else (
-                           "hip graph per step (ndnet.pipeline.GraphedSegmentation)" if args.no_pipeline
-                           else f"NDT(batch i) || forward(batch i-1): a hip graph per stage and ring slot "
-                                f"({graphed.R} buffers), one NDT stream + {graphed.F} forward streams (step i's "
-                                f"forward on stream i % {graphed.F}) ordered by events only, joined once per timed "
-                                f"region (ndnet.pipeline.PipelinedSegmentation.replay_steps)"),
-                       "global_batch": B * world, "points": n, "nds": k, "parallelism": f"dp{world} (clouds sharded)",
-                       "dist_backend": args.dist_backend if world > 1 else None,
-                       **({"rehearsal": f"{world} ranks on {ndev} GPU(s)"} if world > ndev else {})},
+        line.update({
             "stages_ms": {nm: round(float(v), 4) for nm, v in zip(stage_names, stage_ms)}
                          | ({"pointnet_fwd": config_lines["C3_forward_only"]["ms_per_step"],
                              "pointnet_fwd_eager": round(fwd_ms, 4)} if config_lines else
@@ -833,7 +886,7 @@ def main() -> None:
             "config_lines": config_lines,
             "cpu_baseline": cpu,
             "pcie_inclusive": pcie,
-        }
+        })
         print(json.dumps(line))
     if dist:
         torch.distributed.destroy_process_group()

@@ -42,6 +42,35 @@ def test_self_launch_c4_shape():
     assert line["shards"] == [[16 * i, 16] for i in range(8)]
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(REPO, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_names_dtype_and_sample(tmp_path):
+    """--dump-outputs: one float32 .npy per returned array, whole when small;
+    above the size cap a fixed sample, the same from call to call."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    out = torch.arange(2 * 5 * 3, dtype=torch.float64).reshape(2, 5, 3)
+    bench.dump_outputs(str(tmp_path / "a"), out, 0)
+    a = np.load(tmp_path / "a" / "log_probs.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, out.numpy().astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "a"), [out, out[:1]], 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["log_probs.npy", "log_probs_level0.rank1.npy",
+                                                  "log_probs_level1.rank1.npy"]
+    big = torch.arange(5000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "b"), big, 0, cap_bytes=4096)
+    bench.dump_outputs(str(tmp_path / "c"), big, 0, cap_bytes=4096)
+    b, c = np.load(tmp_path / "b" / "log_probs.npy"), np.load(tmp_path / "c" / "log_probs.npy")
+    assert 0 < b.nbytes <= 4096 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.array_equal(b, big.numpy()[b.astype(np.int64)])
+
+
 def test_world_size_must_match_gpus():
     r = _bench("--gpus", "2", "--dry-run", env={"WORLD_SIZE": "1"})
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr

@@ -4,10 +4,10 @@
 # steps are chained so the first failure (or time-out) ends the call, and all
 # output goes under gpurun_out/TAG.  Run from the repo root on the GPU box:
 #
-#   bash tools/gpu.sh suite   TAG                 whole -m gpu suite + smoke + default bench
+#   bash tools/gpu.sh suite   TAG                 whole -m gpu suite + smoke + the --full bench
 #                                                 + the 2-rank (gloo, one card) bench rehearsal
 #   bash tools/gpu.sh tests   TAG [pytest args]   selected GPU tests (e.g. tests/test_model.py -k fp32)
-#   bash tools/gpu.sh bench   TAG [bench args]    bench lines (args passed to bench.py)
+#   bash tools/gpu.sh bench   TAG [bench args]    bench line (args passed to bench.py, e.g. --full)
 #   bash tools/gpu.sh final   TAG                 driver command + C5 + L lines + pipelined / isolated stats
 #   bash tools/gpu.sh ab      TAG NAME[:VAR=VAL,VAR=VAL] ...   env A/B on the bench (AB_ARGS: bench args)
 #   bash tools/gpu.sh abfull  TAG NAME[:VAR=VAL,...] ...      the same with the L (other distribution) line
@@ -69,9 +69,9 @@ suite)
   tail -2 $OUT/pytest_gpu.log
   step smoke 200 $OUT/smoke.log python -u -c "import __graft_entry__ as g; g.smoke()"
   tail -1 $OUT/smoke.log
-  step bench 300 $OUT/bench.log python -u bench.py
+  step bench 300 $OUT/bench.log python -u bench.py --full
   line bench $OUT/bench.log
-  step bench2 400 $OUT/bench_2ranks.log python -u bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 \
+  step bench2 400 $OUT/bench_2ranks.log python -u bench.py --full --gpus 2 --dist-backend gloo --steps 20 --warmup 5 \
     --no-cpu-baseline
   tail -1 $OUT/bench_2ranks.log | cut -c1-300
   ;;
@@ -84,24 +84,24 @@ bench)
   tail -1 $OUT/bench.log | cut -c1-600
   ;;
 final)
-  step bench 400 $OUT/bench.log python -u bench.py --gpus 1 --steps 20 --warmup 5
+  step bench 400 $OUT/bench.log python -u bench.py --full --gpus 1 --steps 20 --warmup 5
   line driver $OUT/bench.log
-  step c5 300 $OUT/c5.log python -u bench.py --levels 2000,1000,500 --no-cpu-baseline
+  step c5 300 $OUT/c5.log python -u bench.py --full --levels 2000,1000,500 --no-cpu-baseline
   line C5 $OUT/c5.log
-  step L 300 $OUT/l.log python -u bench.py --kind L --no-cpu-baseline --no-other
+  step L 300 $OUT/l.log python -u bench.py --full --kind L --no-cpu-baseline --no-other
   line L $OUT/l.log
   cd /tmp && export TMPDIR=/tmp
   step prof_pipe 300 $OUT/prof_pipe.log rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_pipe -o run \
-    -- python3 $R/bench.py --no-cpu-baseline --steps 200
+    -- python3 $R/bench.py --full --no-cpu-baseline --steps 200
   step prof_iso 300 $OUT/prof_iso.log rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_iso -o run \
-    -- python3 $R/bench.py --no-cpu-baseline --no-pipeline --steps 200
+    -- python3 $R/bench.py --full --no-cpu-baseline --no-pipeline --steps 200
   ;;
 ab)
   for A in "$@"; do
     V=${A%%:*}
     ENVS=""
     [ "$V" != "$A" ] && ENVS=${A#*:}
-    step $V 200 $OUT/$V.log env ${ENVS//,/ } python bench.py --no-cpu-baseline --no-other --steps 50 ${AB_ARGS}
+    step $V 200 $OUT/$V.log env ${ENVS//,/ } python bench.py --full --no-cpu-baseline --no-other --steps 50 ${AB_ARGS}
     line $V $OUT/$V.log
   done
   ;;
@@ -110,7 +110,7 @@ abfull)  # as ab, with the other distribution's line (the two-NDT-stream L pipel
     V=${A%%:*}
     ENVS=""
     [ "$V" != "$A" ] && ENVS=${A#*:}
-    step $V 300 $OUT/$V.log env ${ENVS//,/ } python bench.py --no-cpu-baseline --steps 100 ${AB_ARGS}
+    step $V 300 $OUT/$V.log env ${ENVS//,/ } python bench.py --full --no-cpu-baseline --steps 100 ${AB_ARGS}
     line $V $OUT/$V.log
   done
   ;;
@@ -118,14 +118,14 @@ variants)
   for V in "$@"; do
     LIBV=""
     [ "$V" != base ] && LIBV=$R/ndt-net_amd/lib/variants/libndnet_amd_$V.so
-    step $V 200 $OUT/$V.log env NDNET_AMD_LIB=$LIBV python bench.py --no-cpu-baseline --no-other --steps 50 ${AB_ARGS}
+    step $V 200 $OUT/$V.log env NDNET_AMD_LIB=$LIBV python bench.py --full --no-cpu-baseline --no-other --steps 50 ${AB_ARGS}
     line $V $OUT/$V.log
   done
   ;;
 trace)
   cd /tmp && export TMPDIR=/tmp
   step trace 300 $OUT/prof.log rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run \
-    -- python3 $R/bench.py --no-pipeline --no-cpu-baseline --no-other "$@"
+    -- python3 $R/bench.py --full --no-pipeline --no-cpu-baseline --no-other "$@"
   tail -1 $OUT/prof.log | cut -c1-300
   python3 $R/tools/trace_summary.py $OUT/prof --skip 3 | head -30
   ;;
@@ -133,7 +133,7 @@ pmc)
   KIND=${1:?ndt|pn|chain|cache|issue}
   case $KIND in
   ndt)  # U dispatches only (the L split would mix L clouds in)
-    pmc_passes $OUT "python3 $R/bench.py --eager --steps 3 --warmup 1 --no-cpu-baseline --no-other" \
+    pmc_passes $OUT "python3 $R/bench.py --full --eager --steps 3 --warmup 1 --no-cpu-baseline --no-other" \
       FETCH_SIZE WRITE_SIZE $SQ_BUSY $GRBM ;;
   pn)
     pmc_passes $OUT "python3 $R/tools/pn_forward.py --reps 3" $SQ_BUSY $SQ_MIX FETCH_SIZE WRITE_SIZE $GRBM ;;
@@ -146,7 +146,7 @@ pmc)
   issue)
     for K in U L; do
       mkdir -p $OUT/$K
-      pmc_passes $OUT/$K "python3 $R/bench.py --eager --kind $K --steps 3 --warmup 1 --no-cpu-baseline --no-other" \
+      pmc_passes $OUT/$K "python3 $R/bench.py --full --eager --kind $K --steps 3 --warmup 1 --no-cpu-baseline --no-other" \
         "SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_LDS,SQ_ACTIVE_INST_VALU,SQ_ACTIVE_INST_SCA,SQ_ACTIVE_INST_LDS,SQ_WAVE_CYCLES,SQ_BUSY_CYCLES"
     done ;;
   kl)  # the KL stage's kernels on L clouds (k_kl_rank_chunks, k_kl_sort / k_kl_merge): issue mix, LDS, waits
