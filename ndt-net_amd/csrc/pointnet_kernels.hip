@@ -1759,6 +1759,7 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
   // activation regions: layer l reads region l & 1 (or the fused-chunk buffer
   // after a fused layer) and writes region (l + 1) & 1
   int w[2] = {args->L[0].K, 0};
+  int pw1 = 0;  // widest split-bf16 input held in region 1 (three planes of pitch K + kPadB)
   bool has_fuse = false;
   int planes = 0, qprec = 0;
   for (int l = 0; l < args->num_layers; l++) {
@@ -1773,6 +1774,7 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
       if (l == 0 || L.K % 32 || args->L[l - 1].N != L.K) PN_ARG_FAIL();
       if (fed) qprec = 1;
       else planes |= 1 << (l & 1);
+      if (!fed && (l & 1) && L.K > pw1) pw1 = L.K;
     }
     if (fed) {
       if (L.K != args->L[l - 1].N || (L.N != 64 && L.N != 128 && L.N != 256) || L.fuse_next) PN_ARG_FAIL();
@@ -1795,7 +1797,11 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
   // region P reads, after its last chunk, so the chunks may start right after
   // P's input inside that region (and run past its end when it is region 1)
   const int r0f = region0_floats(*args, planes);
-  const int r1f = region_floats(args->max_width2, planes & 2);
+  // region 1 is sized here only (the kernel addresses it from region 0's end): its fp32 rows at the
+  // pitch of max_width2, its bf16 planes at their consumer's K -- a wide fp32 last layer (mode 1,
+  // N > 256) beside 256-wide planes then fits the 64-point build
+  const int r1f32 = region_floats(args->max_width2, 0), r1b16 = pw1 ? region_floats(pw1, 1) : 0;
+  const int r1f = r1b16 > r1f32 ? r1b16 : r1f32;
   int fbuf_off = r0f + r1f;
   size_t total = (size_t)r0f + r1f;
   if (has_fuse) {

@@ -23,7 +23,8 @@ Two forward paths:
     log-softmax over the class dim and the loss also run on HIP kernels
     (round 5); what torch still runs per step is listed in DESIGN.md §3.
     ``NDNET_TRAIN_PATH=torch`` selects the torch composition instead (A/B).
-  * anything else (eval-mode autograd, CPU) -> the PyTorch composition below,
+  * anything else (eval-mode autograd, CPU, widths past the eval kernels'
+    capacity: ``pointnet_hip.supports``) -> the PyTorch composition below,
     which is also the fp32 reference the kernels are tested against.
 """
 from __future__ import annotations
@@ -251,9 +252,13 @@ class NDTNetSegmentation(nn.Module):
         if (not self.training and points.is_cuda and self.point_dim == 3
                 and not self._needs_autograd(points, covariances)):
             # a cuda eval forward IS the HIP path: a missing library raises
-            # (ndnet._lib.lib()) instead of silently running the torch composition
+            # (ndnet._lib.lib()) instead of silently running the torch composition.
+            # Only widths the kernels do not take (pointnet_hip.supports: feature_dim
+            # > 1024, more than 447 classes) run the torch composition below, as the
+            # train path's unsupported layouts do (_hip_fc)
             from . import pointnet_hip
-            return pointnet_hip.segmentation_forward(self, points, covariances)
+            if pointnet_hip.supports(self):
+                return pointnet_hip.segmentation_forward(self, points, covariances)
         return self.forward_torch(points, covariances)
 
     def train(self, mode: bool = True):

@@ -74,6 +74,26 @@ set_precision(os.environ.get("NDNET_PN_PRECISION", "x6"))
 X6_NARROW = os.environ.get("NDNET_PN_X6_NARROW", "1") == "1"
 
 
+# Model widths the eval kernels take (``supports``).  feature_dim: the seg
+# head's global-feature bias is one ndnet_pn_fc_mfma_run with K = F (<= 1024),
+# and the 32-point chain build stages a layer's bias two values per thread
+# (N <= 1024); any F up to that runs (padded to 16 / 64 columns with zeros).
+# num_classes: chain D's logits are fp32 rows of LDS region 1 beside its
+# 256-wide bf16 planes; 64 points x 448 columns is what the 64-point build's
+# 160 KB hold.  A model outside these runs ndtnet's torch composition.
+MAX_FEATURE_DIM = 1024
+MAX_LAST_N = 448
+X6_LAST_MAX_N = 64  # 128 -> C+1 as a split-bf16 layer up to this padded width (_Folded)
+
+
+def supports(model) -> bool:
+    """Whether the eval kernels take this model's widths; if not, the model's
+    forward runs the torch composition (``forward_torch``) instead."""
+    F, C1 = model.feature_dim, model.num_classes + 1
+    return (1 <= F <= MAX_FEATURE_DIM and (FC_MFMA or F % 4 == 0)  # the GEMV kernel reads 16-byte pieces
+            and _npad(C1) <= MAX_LAST_N)
+
+
 class _Layer(ctypes.Structure):
     _fields_ = [("w", ctypes.c_void_p), ("w_cloud_stride", ctypes.c_int64), ("bias", ctypes.c_void_p),
                 ("bias_cloud_stride", ctypes.c_int64), ("K", ctypes.c_int32), ("N", ctypes.c_int32),
@@ -230,12 +250,22 @@ class _Folded:
             self.wide = [self.A[2][0], self.B_tail[2][0], self.C_tail[0], self.D_tail[0][0], self.D_tail[1][0],
                          self.C_mid[0], self.s1aT]
             if X6_NARROW:  # the K >= 64 fp32-MFMA layers too (64 -> 128 of TNet(3) / TNet(64), 64 -> 64, 128 -> C+1)
-                self.wide += [self.A[1][0], self.B_tail[0][0], self.B_tail[1][0], self.D_tail[2][0]]
+                self.wide += [self.A[1][0], self.B_tail[0][0], self.B_tail[1][0]]
+                # 128 -> C+1 only up to 64 padded columns: as a split-bf16 layer its input is three
+                # 128-wide bf16 planes (54 KB in the 64-point build) next to chain D's 256-wide
+                # planes (102 KB), which with the biases fills the 160 KB of LDS at N = 64 exactly;
+                # a wider last layer reads fp32 rows (34 KB)
+                if self.D_tail[2][0].shape[1] <= X6_LAST_MAX_N:
+                    self.wide.append(self.D_tail[2][0])
             self.frag6 = {id(w): _frag_x6(w) for w in self.wide}
             # the FC layers of the TNet heads and the seg head's global-feature
-            # bias, W^T fragment-major for the MFMA GEMV (ndnet_pn_fc_mfma_run)
+            # bias, W^T fragment-major for the MFMA GEMV (ndnet_pn_fc_mfma_run);
+            # the latter's K = F padded to a multiple of 16 with zero rows: the
+            # layer then reads g3's padded columns, which chain C leaves at 0
+            # (zero weight columns and bias, no ReLU)
             self.fcf = {id(w): _frag(w.t().contiguous()) for w in
-                        (self.t1["f1"], self.t1["f2"], self.t2["f1"], self.t2["f2"], self.t2["f3"], self.s1g)}
+                        (self.t1["f1"], self.t1["f2"], self.t2["f1"], self.t2["f2"], self.t2["f3"])}
+            self.fcf[id(self.s1g)] = _frag(_wT(self.s1g, _pad(F, 16), 512))
             # the identity the TNet heads add (ndtnet.py:59), folded into fc3's bias
             self.t1["c3"] = self.t1["c3"] + torch.eye(3, device=dev).reshape(-1)
             self.t2["c3"] = self.t2["c3"] + torch.eye(64, device=dev).reshape(-1)
@@ -312,7 +342,7 @@ class _Folded:
         fcs = (self.t1["f1"], self.t1["f2"], self.t2["f1"], self.t2["f2"], self.t2["f3"], self.s1g)
         for w in fcs:
             layer, bn, k0, K = src[id(w)]
-            add(1, self.fcf[id(w)], layer, bn, k0, K, w.shape[1], w.shape[0])
+            add(1, self.fcf[id(w)], layer, bn, k0, K, _pad(w.shape[1], 16), w.shape[0])
         return jobs
 
     def can_refold(self, tensors) -> bool:
@@ -576,15 +606,17 @@ FC_MFMA = os.environ.get("NDNET_PN_FC", "mfma") == "mfma"
 
 def _fc(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor, relu: bool, wf=None) -> None:
     """out = act(x @ w^T + b) on a HIP kernel (chunks of 16 clouds); wf: W^T
-    fragment-major (the MFMA kernel), else the GEMV kernel on w."""
+    fragment-major (the MFMA kernel; its K is w's padded to a multiple of 16
+    with zero rows, and x's row must be readable -- and finite -- that far),
+    else the GEMV kernel on w."""
     B = x.shape[0]
     st = _lib.stream_ptr(x.device)
     for c0 in range(0, B, 16):
         n = min(16, B - c0)
         if FC_MFMA and wf is not None:
             rc = _lib.lib().ndnet_pn_fc_mfma_run(x[c0].data_ptr(), x.stride(0), wf.data_ptr(), b.data_ptr(),
-                                                 out[c0].data_ptr(), out.stride(0), n, w.shape[1], w.shape[0],
-                                                 1 if relu else 0, st)
+                                                 out[c0].data_ptr(), out.stride(0), n, _pad(w.shape[1], 16),
+                                                 w.shape[0], 1 if relu else 0, st)
             _lib.check(rc, "ndnet_pn_fc_mfma_run")
         else:
             rc = _lib.lib().ndnet_pn_fc_run(x[c0].data_ptr(), x.stride(0), w.data_ptr(), b.data_ptr(),

@@ -64,6 +64,46 @@ def test_folded_algebra_cpu(name):
     assert np.abs(out.numpy() - z["out_eval"]).max() < TOL
 
 
+@pytest.mark.parametrize("F,C", [(100, 28), (1024, 16), (16, 2), (512, 64), (1024, 300)])
+def test_folded_algebra_cpu_other_widths(F, C):
+    """The same folding at widths the fixtures do not have -- feature_dim = 100
+    is no multiple of 16 (the seg head's global-feature FC pads its K to 112),
+    C + 1 = 65 and 301 keep the last layer on the fp32 MFMA -- against
+    forward_torch; the dispatch predicate takes all of them."""
+    from ndnet.models import pointnet_hip as ph
+    m = _model(F, C)
+    assert ph.supports(m)
+    W = ph._Folded(m)
+    Kp = (F + 15) // 16 * 16
+    f = W.fcf[id(W.s1g)]
+    assert f.numel() == Kp * 512
+    if Kp == F:
+        assert torch.equal(f, ph._frag(W.s1g.t().contiguous()))
+    else:  # rows F .. Kp of W^T are zero, the rest is s1g^T
+        wT = torch.zeros(Kp, 512)
+        wT[:F] = W.s1g.t()
+        assert torch.equal(f, ph._frag(wT))
+    assert (id(W.D_tail[2][0]) in W.frag6) == (W.D_tail[2][0].shape[1] <= 64)
+    g = torch.Generator().manual_seed(F + C)
+    p, c = torch.rand((2, 77, 3), generator=g) * 20 - 10, torch.randn((2, 77, 9), generator=g)
+    with torch.no_grad():
+        out = ph.segmentation_forward(m, p, c, chain=ph._chain_torch)
+        ref = m.forward_torch(p, c)
+    err = (out - ref).abs().max().item()
+    print(f"F={F} C={C}: emulation vs forward_torch {err:.3e}")
+    assert out.shape == (2, 77, C + 1) and err < TOL
+
+
+def test_dispatch_predicate_bounds():
+    """Widths past the kernels' capacity take the torch composition (CPU: the
+    predicate only; the GPU half is test_hip_forward_feature_dims_outside_the_tiles)."""
+    from ndnet.models import pointnet_hip as ph
+    from ndnet.models.ndtnet import NDTNetSegmentation
+    assert ph.supports(NDTNetSegmentation(3, 28, 100)) and ph.supports(NDTNetSegmentation())
+    assert ph.supports(NDTNetSegmentation(3, 447, 1024)) and not ph.supports(NDTNetSegmentation(3, 448, 64))
+    assert not ph.supports(NDTNetSegmentation(3, 28, 2048)) and not ph.supports(NDTNetSegmentation(3, 28, 1025))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["ndtnet_seg_F768_C28.npz", "ndtnet_seg_F64_C5.npz"])
 def test_hip_forward_matches_reference_fixture(name):
@@ -98,6 +138,83 @@ def test_hip_forward_matches_torch_fp32(B, N):
     top2 = ref.topk(2, dim=-1).values
     clear = (top2[..., 0] - top2[..., 1]) > 2 * TOL
     assert torch.equal(out.argmax(-1)[clear], ref.argmax(-1)[clear])
+
+
+def _forward_checked(monkeypatch, m, p, c, chains, torch_calls):
+    """model(p, c) on both chain builds against a float64 forward_torch of a
+    deep copy: as close to float64 as torch's own fp32 forward is (factor 3
+    for the summation order, as tests/test_pn_chain.py), within the project's
+    1e-4, and the same class wherever float64's top two are 2e-4 apart.
+    `chains` / `torch_calls`: the chain launches and forward_torch calls one
+    forward must make (which path it takes)."""
+    import copy
+    from ndnet.models import pointnet_hip as ph
+    with torch.no_grad():
+        ref64 = copy.deepcopy(m).double().forward_torch(p.double(), c.double())
+        e_t = (m.forward_torch(p, c).double() - ref64).abs().max().item()
+    count = {"chain": 0, "torch": 0}
+    real_chain, real_torch = ph._run_chain, m.forward_torch
+
+    def spy_chain(*a, **k):
+        count["chain"] += 1
+        return real_chain(*a, **k)
+
+    def spy_torch(*a, **k):
+        count["torch"] += 1
+        return real_torch(*a, **k)
+
+    monkeypatch.setattr(ph, "_run_chain", spy_chain)
+    monkeypatch.setattr(m, "forward_torch", spy_torch)
+    top2 = ref64.topk(2, dim=-1).values if ref64.shape[-1] > 1 else None
+    for t32 in (False, True):
+        monkeypatch.setattr(ph, "_use_t32", lambda b, n, d, f=t32: f)
+        count.update(chain=0, torch=0)
+        with torch.no_grad():
+            out = m(p, c)
+        assert (count["chain"], count["torch"]) == (chains, torch_calls)
+        assert out.shape == ref64.shape and out.dtype == torch.float32
+        e_hip = (out.double() - ref64).abs().max().item()
+        print(f"{'t32' if t32 else 't64'}: e_hip {e_hip:.3e} e_torch_fp32 {e_t:.3e}")
+        assert e_hip <= 3 * e_t + 1e-6
+        assert e_hip < TOL
+        if top2 is not None:
+            clear = (top2[..., 0] - top2[..., 1]) > 2 * TOL
+            assert torch.equal(out.argmax(-1)[clear], ref64.argmax(-1)[clear])
+
+
+def _nd_inputs(B, N, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return (torch.rand((B, N, 3), device="cuda", generator=g) * 20 - 10,
+            torch.randn((B, N, 9), device="cuda", generator=g))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,N", [(2, 77), (3, 130)])
+@pytest.mark.parametrize("F,C", [(1024, 16), (128, 31), (256, 32), (80, 1), (96, 63), (512, 64), (16, 2),
+                                 (1024, 300)])
+def test_hip_forward_model_shapes(monkeypatch, F, C, B, N):
+    """Model widths other than the two fixtures', the constructor's defaults
+    first: every split of the pooled layer (F = 1024, 512, 256, 128 / 80 / 96
+    padded to 128, 16 padded to 32) and of the last layer (C + 1 = 2 .. 301:
+    32, 64, 128 and 320 columns), on the 64-point and the 32-point build."""
+    from ndnet.models import pointnet_hip as ph
+    m = _model(F, C, "cuda")
+    assert ph.supports(m)
+    _forward_checked(monkeypatch, m, *_nd_inputs(B, N, F + C + N), chains=4, torch_calls=0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F,C,path", [(100, 28, "hip"), (2048, 28, "torch")])
+def test_hip_forward_feature_dims_outside_the_tiles(monkeypatch, F, C, path):
+    """feature_dim = 100 (no multiple of 16: the seg head's global-feature FC
+    runs on K padded to 112 over g3's zero columns) stays on the kernels;
+    feature_dim = 2048 (past the FC kernel's K and the chain's bias staging)
+    takes the torch composition.  Neither raises; both are as accurate."""
+    from ndnet.models import pointnet_hip as ph
+    m = _model(F, C, "cuda")
+    assert ph.supports(m) == (path == "hip")
+    chains, torch_calls = (4, 0) if path == "hip" else (0, 1)
+    _forward_checked(monkeypatch, m, *_nd_inputs(3, 130, F), chains=chains, torch_calls=torch_calls)
 
 
 @pytest.mark.gpu
@@ -139,7 +256,7 @@ def test_hip_forward_on_c2_rows(kind):
     assert torch.equal(out.argmax(-1)[clear], ref.argmax(-1)[clear])
 
 
-@pytest.mark.parametrize("F,C", [(768, 28), (64, 5)])
+@pytest.mark.parametrize("F,C", [(768, 28), (64, 5), (100, 28)])
 def test_fold_jobs_cover_every_folded_tensor(F, C):
     """The re-fold's job list (ndnet_pn_fold_job per output, the kernel's
     launch on the GPU): each job writes exactly its output tensor's elements,
@@ -181,7 +298,7 @@ def _perturb(m, seed, versions=True, params=True):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("F,C", [(768, 28), (64, 5)])
+@pytest.mark.parametrize("F,C", [(768, 28), (64, 5), (100, 28)])
 def test_refold_in_place_equals_fresh_fold(F, C):
     """ndnet_pn_fold_run (one launch) re-folds changed weights and running
     statistics into the SAME tensors; every one of them equals what a fresh

@@ -467,6 +467,37 @@ def test_segmentation_train_forward_backward_matches_torch(monkeypatch):
     assert math.isfinite(out.sum().item())
 
 
+@pytest.mark.parametrize("F,C", [(1024, 16), (96, 63)])
+def test_segmentation_train_forward_other_model_shapes(monkeypatch, F, C):
+    """The train-mode forward on the HIP train kernels at the constructor's
+    default widths and at (96, 63) -- 64 output channels, the branch that
+    leaves log_softmax to torch (more than 32) -- against the torch
+    composition and a float64 copy: as close to float64 as torch's fp32 is."""
+    from ndnet.models import ndtnet, train_hip
+    torch.manual_seed(F + C)
+    model = ndtnet.NDTNetSegmentation(num_classes=C, feature_dim=F).cuda().train()
+    ref_model, f64_model = copy.deepcopy(model), copy.deepcopy(model).double()
+    pts, cov = _nds(4, 200, F + C)
+    calls = []
+    real_conv, real_lsm = train_hip.conv_bn_act, train_hip.log_softmax_c
+    monkeypatch.setattr(train_hip, "conv_bn_act", lambda *a, **k: (calls.append("conv"), real_conv(*a, **k))[1])
+    monkeypatch.setattr(train_hip, "log_softmax_c", lambda *a, **k: (calls.append("lsm"), real_lsm(*a, **k))[1])
+    with torch.no_grad():
+        out = model(pts, cov)
+        assert calls.count("conv") >= 9, "the conv blocks ran on the HIP train kernels"
+        assert calls.count("lsm") == (1 if C + 1 <= 32 else 0)
+        monkeypatch.setattr(ndtnet, "_TRAIN_TORCH", True)
+        n = len(calls)
+        ref = ref_model(pts, cov)
+        f64 = f64_model(pts.double(), cov.double())
+        assert len(calls) == n
+    assert out.shape == (4, 200, C + 1)
+    e_hip = (out.double() - f64).abs().max().item()
+    e_torch = (ref.double() - f64).abs().max().item()
+    print(f"F={F} C={C}: max |log-prob error| vs float64: HIP {e_hip:.3e}, torch fp32 {e_torch:.3e}")
+    assert e_hip <= 2 * e_torch + 1e-6, (e_hip, e_torch)
+
+
 def test_block_with_cloud_bias_matches_concat():
     """The segmentation head's conv1 over cat(x_t2, g broadcast) (ndtnet.py:230-234)
     as a 64-channel block plus the per-cloud bias W[:, 64:] g + b."""
