@@ -173,11 +173,14 @@ int ndnet_tr_point_transform_bwd(const float *dx, const float *pts, int pld, con
  * (1 - b2) g^2, p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
  * with t the new step and lr a device float (g += wd p first when
  * weight_decay != 0).  The arrays are host arrays of device pointers; the
- * launches take them by value (graph-capturable, no table upload).  The betas
- * come as doubles: 1 - beta is rounded from double, as torch's kernel gets it. */
+ * launches take them by value (graph-capturable, no table upload).  The
+ * hyperparameters come as doubles, as torch's kernel takes them: each of the
+ * three updates is evaluated in double and rounded to fp32 once, which makes
+ * the result that of torch's kernel.  Every tensor is checked before the
+ * first launch: a rejected call has changed nothing. */
 int ndnet_tr_adam(int n, float *const *params, const float *const *grads, float *const *exp_avg,
                   float *const *exp_avg_sq, float *const *steps, const int64_t *numel, const float *lr, double beta1,
-                  double beta2, float eps, float weight_decay, void *stream);
+                  double beta2, double eps, double weight_decay, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1384,10 +1384,16 @@ __global__ __launch_bounds__(kPtBwdT) void k_tr_point_transform_bwd(const float*
 //
 // torch's fused Adam ran as two multi_tensor_apply launches of ~46 us each on
 // the 3.37 M parameters (94 MB of state traffic: ~15 us at HBM speed, r05p).
-// Per element, torch's order of operations (ATen fused_adam_utils,
-// ADAM_MODE::ORIGINAL): m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g^2;
-// p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps), t the step
-// after its increment (k_tr_adam_steps runs first).
+// Per element, torch's order of operations and its roundings (ATen
+// fused_adam_utils, ADAM_MODE::ORIGINAL): the hyperparameters are doubles
+// there, so g += wd p, m = b1 m + (1 - b1) g and v = b2 v + (1 - b2) g g are
+// each evaluated in double and rounded to fp32 once; the bias corrections
+// 1 - b1^t and sqrt(1 - b2^t) are computed in double and rounded to fp32;
+// step = fp32(lr / bc1), denom = fp32(sqrtf(v) / bc2s + eps),
+// p -= step m / denom in fp32; t the step after its increment
+// (k_tr_adam_steps runs first).  (The earlier fp32 form of the three updates was
+// within an ulp of this per step, but a gradient that nearly cancels against
+// wd p amplified the difference: v off by 1.4e-6 relative after three steps.)
 constexpr int kAdamMax = 32;
 constexpr int kAdamChunk = 4096;  // elements per workgroup (256 threads x 16)
 struct AdamArgs {
@@ -1399,8 +1405,7 @@ struct AdamArgs {
   int64_t numel[kAdamMax];
   int chunk0[kAdamMax + 1];  // first chunk of each tensor; chunk0[n] = total
   int n;
-  float beta1, beta2, omb1, omb2, eps, wd;  // omb = 1 - beta, rounded from double (as torch passes it)
-  double beta1d, beta2d;                    // the bias corrections' powers, in double as torch's kernel
+  double beta1d, beta2d, epsd, wdd;  // doubles, as torch's kernel takes them
   const float* lr;
 };
 
@@ -1420,9 +1425,9 @@ __global__ __launch_bounds__(256) void k_tr_adam(AdamArgs A) {
   const int64_t e0 = (int64_t)(chunk - A.chunk0[ti]) * kAdamChunk;
   const int64_t ne = A.numel[ti];
   const float t = A.step[ti][0];
-  const float lr = A.lr[0];
-  const float bc1 = (float)(1.0 - pow(A.beta1d, (double)t)), bc2 = (float)(1.0 - pow(A.beta2d, (double)t));
-  const float step_size = lr / bc1, bc2s = sqrtf(bc2);
+  const float bc1 = (float)(1.0 - pow(A.beta1d, (double)t)), bc2s = (float)sqrt(1.0 - pow(A.beta2d, (double)t));
+  const float step_size = (float)((double)A.lr[0] / (double)bc1);
+  const double omb1 = 1.0 - A.beta1d, omb2 = 1.0 - A.beta2d;
   float* __restrict__ p = A.p[ti];
   const float* __restrict__ g = A.g[ti];
   float* __restrict__ m = A.m[ti];
@@ -1445,10 +1450,10 @@ __global__ __launch_bounds__(256) void k_tr_adam(AdamArgs A) {
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       float gi = gv[u];
-      if (A.wd != 0.0f) gi = gi + pv[u] * A.wd;
-      const float mi = A.beta1 * mv[u] + A.omb1 * gi;
-      const float vi = A.beta2 * vv[u] + A.omb2 * gi * gi;
-      const float denom = sqrtf(vi) / bc2s + A.eps;
+      if (A.wdd != 0.0) gi = (float)((double)gi + (double)pv[u] * A.wdd);
+      const float mi = (float)(A.beta1d * (double)mv[u] + omb1 * (double)gi);
+      const float vi = (float)(A.beta2d * (double)vv[u] + omb2 * (double)gi * (double)gi);
+      const float denom = (float)((double)(sqrtf(vi) / bc2s) + A.epsd);
       if (ix[u] < ne) {
         m[ix[u]] = mi;
         v[ix[u]] = vi;
@@ -1774,16 +1779,23 @@ extern "C" int ndnet_tr_nll_onehot_bwd(const float* gt, const float* dloss, floa
 
 extern "C" int ndnet_tr_adam(int n, float* const* params, const float* const* grads, float* const* exp_avg,
                              float* const* exp_avg_sq, float* const* steps, const int64_t* numel, const float* lr,
-                             double beta1, double beta2, float eps, float weight_decay, void* stream) {
+                             double beta1, double beta2, double eps, double weight_decay, void* stream) {
   if (n <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || !steps || !numel || !lr) return -20;
+  // every tensor is checked before the first launch: a rejected call has bumped
+  // no step count and updated no tensor
+  for (int b0 = 0; b0 < n; b0 += kAdamMax) {
+    int64_t chunks = 0;
+    for (int j = b0; j < n && j < b0 + kAdamMax; j++) {
+      if (!params[j] || !grads[j] || !exp_avg[j] || !exp_avg_sq[j] || !steps[j] || numel[j] <= 0) return -20;
+      chunks += (numel[j] + kAdamChunk - 1) / kAdamChunk;
+      if (chunks > INT32_MAX) return -20;
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   for (int b0 = 0; b0 < n; b0 += kAdamStepsMax) {  // one launch for every step count (<= 128 tensors)
     AdamSteps S;
     S.n = n - b0 < kAdamStepsMax ? n - b0 : kAdamStepsMax;
-    for (int i = 0; i < S.n; i++) {
-      if (!steps[b0 + i]) return -20;
-      S.s[i] = steps[b0 + i];
-    }
+    for (int i = 0; i < S.n; i++) S.s[i] = steps[b0 + i];
     k_tr_adam_steps<<<1, 64, 0, st>>>(S);
   }
   for (int b0 = 0; b0 < n; b0 += kAdamMax) {
@@ -1792,7 +1804,6 @@ extern "C" int ndnet_tr_adam(int n, float* const* params, const float* const* gr
     int64_t chunks = 0;
     for (int i = 0; i < A.n; i++) {
       const int j = b0 + i;
-      if (!params[j] || !grads[j] || !exp_avg[j] || !exp_avg_sq[j] || !steps[j] || numel[j] <= 0) return -20;
       A.p[i] = params[j];
       A.g[i] = grads[j];
       A.m[i] = exp_avg[j];
@@ -1801,17 +1812,12 @@ extern "C" int ndnet_tr_adam(int n, float* const* params, const float* const* gr
       A.numel[i] = numel[j];
       A.chunk0[i] = (int)chunks;
       chunks += (numel[j] + kAdamChunk - 1) / kAdamChunk;
-      if (chunks > INT32_MAX) return -20;
     }
     A.chunk0[A.n] = (int)chunks;
-    A.beta1 = (float)beta1;
-    A.beta2 = (float)beta2;
-    A.omb1 = (float)(1.0 - beta1);
-    A.omb2 = (float)(1.0 - beta2);
     A.beta1d = beta1;
     A.beta2d = beta2;
-    A.eps = eps;
-    A.wd = weight_decay;
+    A.epsd = eps;
+    A.wdd = weight_decay;
     A.lr = lr;
     k_tr_adam<<<(unsigned)chunks, 256, 0, st>>>(A);
   }

@@ -527,7 +527,8 @@ def test_block_with_cloud_bias_matches_concat():
 @pytest.mark.parametrize("cin,cout,relu,B,N", [
     (128, 1024, True, 16, 1000),   # TNet conv3 -> amax (ndtnet.py:50-51)
     (128, 768, False, 4, 1000),    # NDTNet conv3 -> the seg head's global max (:152, :231)
-    (64, 128, True, 20, 700),      # uncached BatchNorm path
+    (64, 128, True, 20, 700),      # 14000 values per channel: still the cached walk, N % 4 == 0
+    (64, 128, True, 20, 1000),     # 20000 > 16384 values per channel: the uncached pooled BatchNorm path
 ])
 def test_pooled_block_matches_amax(cin, cout, relu, B, N):
     """conv_bn_act_pool == relu(bn(conv(x))).amax(dim=2): pooled values, running
