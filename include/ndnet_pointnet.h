@@ -39,8 +39,20 @@ typedef struct ndnet_pn_layer {
                           // 1: split-bf16 "x6" (fp32-accurate, v_mfma_f32_16x16x32_bf16): K % 32 == 0,
                           //    `w` = bf16 [N/16][K/32][3 planes][64 lanes][8] with W^T = h + m + l and
                           //    lane l's 8 values W^T[32 kg + 8 (l/16) + j][16 cb + l%16]; the layer's
-                          //    producer must be the previous, unfused layer (it stores bf16 planes)
-  int32_t fuse_next;      // 1: this layer's output (N % 64 == 0) is produced in 64-column chunks, each
+                          //    producer must be the previous, unfused layer (it stores bf16 planes).
+                          //    Per operand pair x = h + m + l, y = h' + m' + l' it keeps the six products
+                          //    mm', mh', lh', hl', hm', hh' (dropped: < 3 * 2^-24 |x y|, fp32's own rounding)
+                          // 2: split-bf16 "x3": the products mh', hm', hh' of the same planes (16 significant
+                          //    bits per operand); dropped terms <= 3.02 * 2^-18 |x y| per product
+                          // 3: split-bf16 "x1": hh' only -- plain bf16 operands, fp32 accumulation; dropped
+                          //    terms <= (2^-8 + 2^-18) |x y| per product
+                          //    (from |x - h| <= 2^-9 |x|, |x - h - m| <= 2^-18 |x|, round to nearest even)
+                          //    2 and 3 read the prec 1 weights as they are (NDNET_FOLD_FRAG6: one fold
+                          //    serves the three modes; the planes a mode does not use are never loaded)
+                          //    under the constraints of prec 1.  All layers of a chain with prec != 0 carry
+                          //    the same prec (each mode is an instantiation of the whole kernel; prec 1's is
+                          //    the code it was without the others); prec 0 layers mix freely with them
+  int32_t fuse_next;     // 1: this layer's output (N % 64 == 0) is produced in 64-column chunks, each
                           // consumed at once by the next layer (whose N is 64, 128 or 256) -- the
                           // activation never occupies LDS whole
 } ndnet_pn_layer;
@@ -92,7 +104,8 @@ typedef struct ndnet_pn_chain {
 
 /* Runs one chain over `batch` clouds on `stream` (a hipStream_t; NULL = default
  * stream).  Returns 0, NDNET_ERR_ARG (-20) for an inconsistent argument block
- * (layer sizes, LDS region widths) or NDNET_ERR_HIP (-21) on a launch failure.
+ * (layer sizes, LDS region widths, a prec above 3, split layers of different
+ * prec in one chain) or NDNET_ERR_HIP (-21) on a launch failure.
  * No allocation, no synchronisation: graph-capturable. */
 int ndnet_pn_chain_run(const ndnet_pn_chain *args, int batch, void *stream);
 /* The same chain on 32-point tiles (8 waves per workgroup; same arguments,
@@ -137,7 +150,7 @@ int ndnet_pn_fc_mfma_run(const float *in, int ld_in, const float *Wf, const floa
  * rounded fp32 operation as torch computes the fold.  Kinds:
  *   NDNET_FOLD_WT     out[k][n] (Kp x Np floats) = fw(n, k), zero padded
  *   NDNET_FOLD_FRAG   the same W^T fragment-major (ndnet_pn_layer.w, prec 0)
- *   NDNET_FOLD_FRAG6  the same W^T split-bf16 (ndnet_pn_layer.w, prec 1;
+ *   NDNET_FOLD_FRAG6  the same W^T split-bf16 (ndnet_pn_layer.w, prec 1, 2 and 3;
  *                     bf16 rounding to nearest even, residuals exact)
  *   NDNET_FOLD_ROWS   out[n][k] (N x K floats) = fw(n, k)
  *   NDNET_FOLD_BASIS  TNet(3)'s t1 basis of conv1 (K == 12):

@@ -192,19 +192,19 @@ __device__ unsigned long long g_pn_stamps[kStampWgs][16];
 // barrier inside a layer) and only the activations live in LDS.
 struct LayerCtx {
   const f32x4* __restrict__ w;     // this cloud's fragments, offset by the lane (prec 0)
-  const bf16x8* __restrict__ w6;   // split-bf16 fragments, offset by the lane (prec 1)
+  const bf16x8* __restrict__ w6;   // split-bf16 fragments, offset by the lane (prec 1..3)
   const float* __restrict__ bias;
-  int KG, N, relu, prec;           // KG: 16-row k-groups (prec 0) or 32-row (prec 1)
+  int KG, N, relu, prec;           // KG: 16-row k-groups (prec 0) or 32-row (prec 1..3)
 };
 
 // bias: the layer's (this cloud's) bias, staged in LDS by the kernel's prologue
 // The first weight step of a layer, loaded by each wave before the barrier
 // that closes the previous layer (its latency hides behind the barrier wait;
 // 16-wave 64-point build, where every layer's wave tile is one column block):
-// r0..r2 = the three bf16x8 planes for prec 1, r0 for prec 0.
+// r0..r2 = the bf16x8 planes the mode reads for prec 1..3, r0 for prec 0.
 struct Pre {
   bool on;
-  f32x4 r0, r1, r2;  // prec 1: bf16x8 planes h, m, l (bit_cast); prec 0: r0
+  f32x4 r0, r1, r2;  // prec 1..3: bf16x8 planes h, m, l (bit_cast); prec 0: r0
 };
 
 __device__ inline LayerCtx layer_ctx(const ndnet_pn_chain& A, int l, int b, const float* bias) {
@@ -214,7 +214,7 @@ __device__ inline LayerCtx layer_ctx(const ndnet_pn_chain& A, int l, int b, cons
   C.w6 = reinterpret_cast<const bf16x8*>(L.w + (int64_t)b * L.w_cloud_stride) + (pn_tid() & 63);
   C.bias = bias;
   C.prec = L.prec;
-  C.KG = L.prec ? L.K / 32 : L.K / 16;  // prec 1 and 2: 32-row k-groups
+  C.KG = L.prec ? L.K / 32 : L.K / 16;  // split-bf16: 32-row k-groups
   C.N = L.N;
   C.relu = L.relu;
   return C;
@@ -448,9 +448,39 @@ __device__ inline void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
   l = (__bf16)(r - (float)m);
 }
 
-// Bias + ReLU of this wave's tile into the three bf16 planes of a region
-// (`out` in floats; pitch in bf16).
-template <int RB, int NB>
+// The reduced modes (ndnet_pn_layer.prec 2 / 3) keep fewer of those products,
+// on the same planes and the same weight layout.  T is the number of terms,
+// a compile-time parameter of everything below and of the whole kernel (all
+// split layers of a chain share one mode, so T = 6 compiles to the code it
+// was before the modes existed):
+//   T = 6 (prec 1)  mm, mh, lh, hl, hm, hh   planes h, m, l
+//   T = 3 (prec 2)  mh, hm, hh               planes h, m: 16 significant bits
+//                   per operand, dropped terms <= 3.02 * 2^-18 |x y|
+//   T = 1 (prec 3)  hh                       plane h: plain bf16 operands,
+//                   dropped terms <= (2^-8 + 2^-18) |x y|
+// A plane a mode does not read is neither computed, stored, loaded from LDS
+// or global memory, nor prefetched; the LDS layout (plane p at p * kP * pitch)
+// and the weight layout (three planes per k-group) are the same in all modes.
+template <int T>
+constexpr int kPlanes = T == 6 ? 3 : T == 3 ? 2 : 1;
+
+// v's first kPlanes<T> bf16 planes (l, or m and l, left alone when unused)
+template <int T>
+__device__ inline void split_t(float v, __bf16& h, __bf16& m, __bf16& l) {
+  static_assert(T == 6 || T == 3 || T == 1, "6, 3 or 1 terms");
+  if constexpr (T == 6) {
+    split3(v, h, m, l);
+  } else if constexpr (T == 3) {
+    h = (__bf16)v;
+    m = (__bf16)(v - (float)h);
+  } else {
+    h = (__bf16)v;
+  }
+}
+
+// Bias + ReLU of this wave's tile into the bf16 planes of a region that the
+// consumer's mode reads (`out` in floats; pitch in bf16).
+template <int RB, int NB, int T>
 __device__ __attribute__((always_inline)) inline void store_cols_planes(const f32x4 (&acc)[RB][NB],
                                                                         const float* __restrict__ bias, int col0,
                                                                         int relu, int row0, int out, int pitchb,
@@ -474,16 +504,16 @@ __device__ __attribute__((always_inline)) inline void store_cols_planes(const f3
         float v = acc[rb][j][r] + bv[r];
         if (relu) v = fmaxf(v, 0.0f);
         __bf16 h, m, l;
-        split3(v, h, m, l);
+        split_t<T>(v, h, m, l);
         h4[r] = h;
-        m4[r] = m;
-        l4[r] = l;
+        if constexpr (T >= 3) m4[r] = m;
+        if constexpr (T == 6) l4[r] = l;
       }
       const int row = row0 + 16 * rb + cl;
       const int e = row * pitchb + plane_col(row, oc0 + 16 * j + 4 * kq);  // 4 channels: 8 bytes
       *reinterpret_cast<bf16x4*>(base + e) = h4;
-      *reinterpret_cast<bf16x4*>(base + plane + e) = m4;
-      *reinterpret_cast<bf16x4*>(base + 2 * plane + e) = l4;
+      if constexpr (T >= 3) *reinterpret_cast<bf16x4*>(base + plane + e) = m4;
+      if constexpr (T == 6) *reinterpret_cast<bf16x4*>(base + 2 * plane + e) = l4;
     }
   }
 #else
@@ -497,12 +527,12 @@ __device__ __attribute__((always_inline)) inline void store_cols_planes(const f3
         float v = acc[rb][j][r] + bv;
         if (relu) v = fmaxf(v, 0.0f);
         __bf16 h, m, l;
-        split3(v, h, m, l);
+        split_t<T>(v, h, m, l);
         const int row = row0 + 16 * rb + 4 * kq + r;
         const int e = row * pitchb + plane_col(row, oc0 + 16 * j + cl);
         base[e] = h;
-        base[plane + e] = m;
-        base[2 * plane + e] = l;
+        if constexpr (T >= 3) base[plane + e] = m;
+        if constexpr (T == 6) base[2 * plane + e] = l;
       }
   }
 #endif
@@ -510,9 +540,10 @@ __device__ __attribute__((always_inline)) inline void store_cols_planes(const f3
 
 // One 32-row k-group: the A planes are read one at a time (m, l, h) so only
 // one plane's fragments are live; per plane the B planes its terms need.
-template <int RB, int NB>
+// T terms, smallest first: 6 as listed above, 3 = m*h, h*m, h*h, 1 = h*h.
+template <int RB, int NB, int T>
 __device__ __attribute__((always_inline)) inline void mma_kgroup_x6(f32x4 (&acc)[RB][NB], const __bf16* a0, int plane,
-                                                                    int rstride, const bf16x8 (&bw)[NB][3]) {
+                                                                    int rstride, const bf16x8 (&bw)[NB][kPlanes<T>]) {
   bf16x8 a[RB];
   auto ld = [&](int p) {
 #ifdef NDNET_PN_EXP_NOA  // timing experiment only (wrong results): A fragments from registers
@@ -532,21 +563,33 @@ __device__ __attribute__((always_inline)) inline void mma_kgroup_x6(f32x4 (&acc)
         acc[rb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rb], bw[j][pb], acc[rb][j], 0, 0, 0);
 #endif
   };
-  ld(1);  // m: m*m, m*h
-  mm(1);
-  mm(0);
-  ld(2);  // l: l*h
-  mm(0);
-  ld(0);  // h: h*l, h*m, h*h
-  mm(2);
-  mm(1);
-  mm(0);
+  if constexpr (T == 6) {
+    ld(1);  // m: m*m, m*h
+    mm(1);
+    mm(0);
+    ld(2);  // l: l*h
+    mm(0);
+    ld(0);  // h: h*l, h*m, h*h
+    mm(2);
+    mm(1);
+    mm(0);
+  } else if constexpr (T == 3) {
+    ld(1);  // m: m*h
+    mm(0);
+    ld(0);  // h: h*m, h*h
+    mm(1);
+    mm(0);
+  } else {
+    ld(0);  // h: h*h
+    mm(0);
+  }
 }
 
-// run_tiles for split-bf16 layers: 32-row k-groups; A from the three planes
-// (abase: this lane's row / k offset in plane 0, in bf16), B three 1 KB
-// fragment pieces per column block, prefetched kDepth6 steps ahead.
-template <int RB, int NB, class Epi, int kD = kDepth6>
+// run_tiles for split-bf16 layers: 32-row k-groups; A from the mode's planes
+// (abase: this lane's row / k offset in plane 0, in bf16), B the mode's 1 KB
+// fragment pieces (of the three stored) per column block, prefetched kDepth6
+// steps ahead.
+template <int T, int RB, int NB, class Epi, int kD = kDepth6>
 __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[RB][NB],
                                                                    const bf16x8* __restrict__ w, int KG, int kg0,
                                                                    int nkg, int cb0, int cbs, int nchunk,
@@ -556,13 +599,13 @@ __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[
   // workgroups in lockstep do not all stream the same weight fragments at
   // once (different chunks hit different L2 lines); each chunk's columns and
   // sums are unchanged
-  const int T = nchunk * nkg;
+  const int NT = nchunk * nkg;  // k-group steps
   const int plane = kP * pitchb;
   const int64_t jstride = (int64_t)KG * 3 * 64;
   const int64_t chunk_jump = ((int64_t)cbs * KG - (nkg - 1)) * 3 * 64;
   const int64_t wrap = (int64_t)nchunk * cbs * KG * 3 * 64;
   const bf16x8* lp = w + ((int64_t)(cb0 + rot * cbs) * KG + kg0) * 3 * 64;
-  int lkk = 0, lleft = T, lc = rot;
+  int lkk = 0, lleft = NT, lc = rot;
   auto advance = [&]() {
     if (lleft > 1) {
       lleft--;
@@ -578,43 +621,44 @@ __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[
       }
     }
   };
-  auto load = [&](bf16x8 (&bw)[NB][3]) {
+  constexpr int NPL = kPlanes<T>;
+  auto load = [&](bf16x8 (&bw)[NB][NPL]) {
 #ifdef NDNET_PN_EXP_NOB  // timing experiment only (wrong results): weights loaded once per layer
-    if (lleft == T)
+    if (lleft == NT)
 #endif
 #pragma unroll
     for (int j = 0; j < NB; j++)
 #pragma unroll
-      for (int p = 0; p < 3; p++) bw[j][p] = lp[j * jstride + p * 64];
+      for (int p = 0; p < NPL; p++) bw[j][p] = lp[j * jstride + p * 64];
     advance();
   };
   int kk = 0, c = rot;
-  auto step = [&](const bf16x8 (&bw)[NB][3]) {
-    mma_kgroup_x6<RB, NB>(acc, abase + 32 * kk, plane, 16 * pitchb, bw);
+  auto step = [&](const bf16x8 (&bw)[NB][NPL]) {
+    mma_kgroup_x6<RB, NB, T>(acc, abase + 32 * kk, plane, 16 * pitchb, bw);
     if (++kk == nkg) {
       epi(acc, c);
       kk = 0;
       if (++c == nchunk) c = 0;
     }
   };
-  bf16x8 bq[kD][NB][3];
+  bf16x8 bq[kD][NB][NPL];
 #pragma unroll
   for (int i = 0; i < kD; i++) {
     if (NB == 1 && i == 0 && pre.on) {  // the first step, prefetched by the caller
       bq[0][0][0] = __builtin_bit_cast(bf16x8, pre.r0);
-      bq[0][0][1] = __builtin_bit_cast(bf16x8, pre.r1);
-      bq[0][0][2] = __builtin_bit_cast(bf16x8, pre.r2);
+      if constexpr (NPL >= 2) bq[0][0][1] = __builtin_bit_cast(bf16x8, pre.r1);
+      if constexpr (NPL == 3) bq[0][0][2] = __builtin_bit_cast(bf16x8, pre.r2);
       advance();
     } else {
       load(bq[i]);
     }
   }
-  for (int t = 0; t < T; t += kD) {
+  for (int t = 0; t < NT; t += kD) {
 #pragma unroll
     for (int i = 0; i < kD; i++) {
-      if (t + i < T) {
+      if (t + i < NT) {
         step(bq[i]);
-        if (t + i + kD < T) load(bq[i]);  // no reload past the last step
+        if (t + i + kD < NT) load(bq[i]);  // no reload past the last step
       }
     }
   }
@@ -622,7 +666,7 @@ __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[
 
 // One layer: RB row blocks x NB column blocks per wave; 4 / RB row groups x
 // 4 RB column groups of waves; N in chunks of (column groups x NB x 16).
-template <int RB, int NB>
+template <int RB, int NB, int T>
 __device__ __attribute__((always_inline)) inline void plain_layer(const LayerCtx& C, int in, int pin, int out, int pout, float* gmax, int rows_valid,
                             bool out_planes, Pre pre = {}) {
   constexpr int WR = kRowBlocks / RB, WC = kWaves / WR, CB = WC * NB;
@@ -638,7 +682,7 @@ __device__ __attribute__((always_inline)) inline void plain_layer(const LayerCtx
   auto epi = [&](f32x4 (&a)[RB][NB], int c) {
     const int col0 = (c * CB + wc * NB) * 16;
     if (gmax) pool_cols<RB, NB>(a, C.bias, col0, C.relu, row0, rows_valid, gmax);
-    else if (out_planes) store_cols_planes<RB, NB>(a, C.bias, col0, C.relu, row0, out, C.N + kPadB, col0);
+    else if (out_planes) store_cols_planes<RB, NB, T>(a, C.bias, col0, C.relu, row0, out, C.N + kPadB, col0);
     else store_cols<RB, NB>(a, C.bias, col0, C.relu, row0, out, pout, col0);
     zero_acc(a);
   };
@@ -652,9 +696,9 @@ __device__ __attribute__((always_inline)) inline void plain_layer(const LayerCtx
     // a layer of two k-group steps (K = 64, one chunk: the narrow 64 -> 64 /
     // 64 -> 128 layers) loads both up front, so only one L2 latency is exposed
     if (NDNET_PN_SHORT_D2 && nchunk * C.KG == 2)
-      run_tiles_x6<RB, NB, decltype(epi), 2>(acc, C.w6, C.KG, 0, C.KG, wc * NB, CB, nchunk, abase6, pb, epi, pre, 0);
+      run_tiles_x6<T, RB, NB, decltype(epi), 2>(acc, C.w6, C.KG, 0, C.KG, wc * NB, CB, nchunk, abase6, pb, epi, pre, 0);
     else
-      run_tiles_x6<RB, NB>(acc, C.w6, C.KG, 0, C.KG, wc * NB, CB, nchunk, abase6, pb, epi, pre,
+      run_tiles_x6<T, RB, NB>(acc, C.w6, C.KG, 0, C.KG, wc * NB, CB, nchunk, abase6, pb, epi, pre,
                            kChunkRot ? (int)((blockIdx.x + blockIdx.y) % nchunk) : 0);
   } else {
     const float* abase = g_smem + in + (row0 + cl) * pin + 4 * kq;
@@ -673,7 +717,7 @@ __host__ __device__ inline int fbuf_floats(int qprec) {
 // consumed at once as 4 k-groups of layer Q (N1 -> N2 = one chunk of Q's
 // (RB, NB) split), whose accumulators persist across the chunks: the N1-wide
 // activation never needs LDS of its own.  One barrier per chunk.
-template <int RB, int NB>
+template <int RB, int NB, int T>
 __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx& P, const LayerCtx& Q, int in, int pin, int fbuf, int out, int pout,
                            float* gmax, int rows_valid, bool out_planes, Pre pre = {}) {
   constexpr int kFP = kFuseNC + kPadF;
@@ -697,12 +741,12 @@ __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx&
     zero_acc(acc1);
     const int fb = fbuf + (f & 1) * fbsz;
     auto epi = [&](f32x4 (&a)[1][PNB], int) {
-      if (Q.prec) store_cols_planes<1, PNB>(a, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fb, kFuseNC + kPadB, 16 * pwc);
+      if (Q.prec) store_cols_planes<1, PNB, T>(a, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fb, kFuseNC + kPadB, 16 * pwc);
       else store_cols<1, PNB>(a, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fb, kFP, 16 * pwc);
     };
     Pre pf = pre;
     if (f != 0) pf.on = false;
-    if (P.prec) run_tiles_x6<1, PNB>(acc1, P.w6, P.KG, 0, P.KG, 4 * f + pwc, 0, 1, ain6, 32 * P.KG + kPadB, epi, pf);
+    if (P.prec) run_tiles_x6<T, 1, PNB>(acc1, P.w6, P.KG, 0, P.KG, 4 * f + pwc, 0, 1, ain6, 32 * P.KG + kPadB, epi, pf);
     else run_tiles<1, PNB>(acc1, P.w, P.KG, 0, P.KG, 4 * f + pwc, 0, 1, ain, pin, epi, pf);
   };
   f32x4 acc2[RB][NB];
@@ -714,7 +758,7 @@ __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx&
       if (Q.prec) {
         const __bf16* af6 = reinterpret_cast<const __bf16*>(g_smem + fbuf + (f & 1) * fbsz) +
                             (qrow0 + cl) * (kFuseNC + kPadB) + plane_col(cl, 8 * kq);
-        run_tiles_x6<RB, NB>(acc2, Q.w6, Q.KG, 2 * f, 2, qwc * NB, 0, 1, af6, kFuseNC + kPadB,
+        run_tiles_x6<T, RB, NB>(acc2, Q.w6, Q.KG, 2 * f, 2, qwc * NB, 0, 1, af6, kFuseNC + kPadB,
                              [](f32x4 (&)[RB][NB], int) {});
       } else {
         const float* af = g_smem + fbuf + (f & 1) * fbsz + (qrow0 + cl) * kFP + 4 * kq;
@@ -726,7 +770,7 @@ __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx&
   }
   if (qidle) return;
   if (gmax) pool_cols<RB, NB>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, rows_valid, gmax);
-  else if (out_planes) store_cols_planes<RB, NB>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc * NB);
+  else if (out_planes) store_cols_planes<RB, NB, T>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc * NB);
   else store_cols<RB, NB>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, out, pout, 16 * qwc * NB);
 }
 
@@ -740,7 +784,7 @@ __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx&
 // 2 k-groups, 3 planes each: 48 VGPRs) are loaded one chunk ahead, right after
 // the previous chunk's MFMAs consumed the registers, so each load has a whole
 // phase and a barrier to arrive.  Same products, same accumulation order.
-template <int RB>
+template <int RB, int T>
 __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const LayerCtx& P, const LayerCtx& Q, int in,
                                                                      int fbuf, int out, int pout, float* gmax,
                                                                      int rows_valid, bool out_planes) {
@@ -757,27 +801,28 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
   const int fbsz = fbuf_floats(1) / 2;
   constexpr int fpb = kFuseNC + kPadB;
   // chunk f's weights: P column block 4 f + pwc, k-groups 0, 1; Q column block qwc, k-groups 2 f, 2 f + 1
-  bf16x8 wp[2][1][3], wq[2][1][3];
+  constexpr int NPL = kPlanes<T>;  // of the three planes stored per k-group
+  bf16x8 wp[2][1][NPL], wq[2][1][NPL];
   auto load_p = [&](int f) {
     const bf16x8* s = P.w6 + ((int64_t)(4 * f + pwc) * P.KG) * 3 * 64;
 #pragma unroll
     for (int k = 0; k < 2; k++)
 #pragma unroll
-      for (int p = 0; p < 3; p++) wp[k][0][p] = s[(k * 3 + p) * 64];
+      for (int p = 0; p < NPL; p++) wp[k][0][p] = s[(k * 3 + p) * 64];
   };
   auto load_q = [&](int f) {
     const bf16x8* s = Q.w6 + ((int64_t)qwc * Q.KG + 2 * f) * 3 * 64;
 #pragma unroll
     for (int k = 0; k < 2; k++)
 #pragma unroll
-      for (int p = 0; p < 3; p++) wq[k][0][p] = s[(k * 3 + p) * 64];
+      for (int p = 0; p < NPL; p++) wq[k][0][p] = s[(k * 3 + p) * 64];
   };
   auto p_chunk = [&](int f) {
     f32x4 acc1[1][1];
     zero_acc(acc1);
 #pragma unroll
-    for (int k = 0; k < 2; k++) mma_kgroup_x6<1, 1>(acc1, ain6 + 32 * k, kP * pinb, 16 * pinb, wp[k]);
-    store_cols_planes<1, 1>(acc1, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fbuf + (f & 1) * fbsz, fpb, 16 * pwc);
+    for (int k = 0; k < 2; k++) mma_kgroup_x6<1, 1, T>(acc1, ain6 + 32 * k, kP * pinb, 16 * pinb, wp[k]);
+    store_cols_planes<1, 1, T>(acc1, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fbuf + (f & 1) * fbsz, fpb, 16 * pwc);
   };
   f32x4 acc2[RB][1];
   zero_acc(acc2);
@@ -798,11 +843,11 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
       if (f + 2 < nf) load_p(f + 2);
     }
 #pragma unroll
-    for (int k = 0; k < 2; k++) mma_kgroup_x6<RB, 1>(acc2, af6 + 32 * k, kP * fpb, 16 * fpb, wq[k]);
+    for (int k = 0; k < 2; k++) mma_kgroup_x6<RB, 1, T>(acc2, af6 + 32 * k, kP * fpb, 16 * fpb, wq[k]);
     if (f + 1 < nf) load_q(f + 1);
 #else
 #pragma unroll
-    for (int k = 0; k < 2; k++) mma_kgroup_x6<RB, 1>(acc2, af6 + 32 * k, kP * fpb, 16 * fpb, wq[k]);
+    for (int k = 0; k < 2; k++) mma_kgroup_x6<RB, 1, T>(acc2, af6 + 32 * k, kP * fpb, 16 * fpb, wq[k]);
     if (f + 1 < nf) {
       load_q(f + 1);
       p_chunk(f + 1);
@@ -812,7 +857,7 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
     __syncthreads();
   }
   if (gmax) pool_cols<RB, 1>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, rows_valid, gmax);
-  else if (out_planes) store_cols_planes<RB, 1>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc);
+  else if (out_planes) store_cols_planes<RB, 1, T>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc);
   else store_cols<RB, 1>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, out, pout, 16 * qwc);
 }
 
@@ -820,6 +865,7 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
 // build; others leave pre off): the column block plain_layer<RB, 1> /
 // fused_pair's first chunk gives the wave, at k-group 0 -- the address
 // run_tiles* would load first.
+template <int T>
 __device__ inline void prefetch_first(const ndnet_pn_chain& A, int l, int b, Pre& pre) {
   pre.on = false;
 #ifndef NDNET_PN_PREFETCH  // off by default: measured 1-2 us slower per chain (profiles/r03e_stamps_ab.txt)
@@ -838,11 +884,11 @@ __device__ inline void prefetch_first(const ndnet_pn_chain& A, int l, int b, Pre
     }
     const int KG = L.prec ? L.K / 32 : L.K / 16;
     const float* wb = L.w + (int64_t)b * L.w_cloud_stride;
-    if (L.prec == 1) {
+    if (L.prec) {  // the planes the mode reads
       const bf16x8* q = reinterpret_cast<const bf16x8*>(wb) + lane + (int64_t)cb0 * KG * 3 * 64;
       pre.r0 = __builtin_bit_cast(f32x4, q[0]);
-      pre.r1 = __builtin_bit_cast(f32x4, q[64]);
-      pre.r2 = __builtin_bit_cast(f32x4, q[128]);
+      if constexpr (T >= 3) pre.r1 = __builtin_bit_cast(f32x4, q[64]);
+      if constexpr (T == 6) pre.r2 = __builtin_bit_cast(f32x4, q[128]);
     } else {
       pre.r0 = (reinterpret_cast<const f32x4*>(wb) + lane + (int64_t)cb0 * KG * 64)[0];
     }
@@ -894,6 +940,10 @@ __host__ __device__ inline int region0_floats(const ndnet_pn_chain& A, int plane
   return valu_layer0(A) && r < kValu0Floats + 16 ? kValu0Floats + 16 : r;
 }
 
+// One instantiation per mode of the chain's split-bf16 layers (T terms):
+// k_pn_chain<6> serves prec 1 and chains with no split layer -- the kernel as
+// it was before the modes, register for register -- <3> prec 2, <1> prec 3.
+template <int T>
 __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int planes, int fbuf, int bias_base) {
   const int b = blockIdx.y;
   const int p0 = blockIdx.x * kP;
@@ -931,7 +981,7 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
   }
   const bool v0 = valu_layer0(A);
   Pre pre;  // the next layer's first weight step (prefetched before each layer barrier)
-  prefetch_first(A, v0 ? 1 : 0, b, pre);
+  prefetch_first<T>(A, v0 ? 1 : 0, b, pre);
   float* const s_w0 = g_smem;  // v0: W0^T [16][64] row-major, in region 0
   // v0: this thread's point rows (t / 16 + pass * kThreads / 16) and 4 output
   // channels (4 (t % 16) ..)
@@ -1082,7 +1132,7 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
         if (A.L[0].relu) acc[j] = fmaxf(acc[j], 0.0f);
       }
       const int out = reg[1];
-      if (A.L[1].prec) {  // three bf16 planes, pitch 64 + kPadB
+      if (A.L[1].prec) {  // the mode's bf16 planes, pitch 64 + kPadB
         typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
         const int pb = 64 + kPadB;
         __bf16* const base = reinterpret_cast<__bf16*>(g_smem + out) + vr * pb + plane_col(vr, 4 * vq);
@@ -1090,14 +1140,14 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           __bf16 hh, mm, ll;
-          split3(acc[j], hh, mm, ll);
+          split_t<T>(acc[j], hh, mm, ll);
           h4[j] = hh;
-          m4[j] = mm;
-          l4[j] = ll;
+          if constexpr (T >= 3) m4[j] = mm;
+          if constexpr (T == 6) l4[j] = ll;
         }
         *reinterpret_cast<bf16x4*>(base) = h4;
-        *reinterpret_cast<bf16x4*>(base + kP * pb) = m4;
-        *reinterpret_cast<bf16x4*>(base + 2 * kP * pb) = l4;
+        if constexpr (T >= 3) *reinterpret_cast<bf16x4*>(base + kP * pb) = m4;
+        if constexpr (T == 6) *reinterpret_cast<bf16x4*>(base + 2 * kP * pb) = l4;
       } else {
         *reinterpret_cast<f32x4*>(g_smem + out + vr * pitch1 + 4 * vq) = acc;
       }
@@ -1127,8 +1177,8 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
       constexpr int kQ = 16 / kWaves > 0 ? 16 / kWaves : 1;
       const bool op = !last && A.L[l + 2].prec;  // the layer after Q reads bf16 planes
       if constexpr (kP == 32) {  // two row blocks: each Q split with half the row groups
-        if (Q.N == 256) fused_pair<2, kQ>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
-        else fused_pair<1, kQ>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
+        if (Q.N == 256) fused_pair<2, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
+        else fused_pair<1, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
       } else {
 #ifndef NDNET_PN_FUSED_PIPE
 #define NDNET_PN_FUSED_PIPE 1
@@ -1136,14 +1186,14 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
         bool piped = false;
         if constexpr (kWaves == 16) {
           if (NDNET_PN_FUSED_PIPE && Q.N == 256 && P.prec && Q.prec && P.KG == 2) {
-            fused_pair_x6p<4>(P, Q, in, fbuf, out, pout, gm, rows_valid, op);
+            fused_pair_x6p<4, T>(P, Q, in, fbuf, out, pout, gm, rows_valid, op);
             piped = true;
           }
         }
         if (piped) {
-        } else if (Q.N == 256) fused_pair<4, kQ>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
-        else if (Q.N > 64) fused_pair<2, kQ>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
-        else fused_pair<1, kQ>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
+        } else if (Q.N == 256) fused_pair<4, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
+        else if (Q.N > 64) fused_pair<2, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
+        else fused_pair<1, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
       }
       l++;
     } else {
@@ -1155,9 +1205,9 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
       if constexpr (kP == 32) {
         // 32-point tiles, 8 waves: two row blocks, columns per wave as the
         // 64-point form's (one row group, all waves across the columns)
-        if (C.N % 256 == 0) plain_layer<2, 2>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 128 == 0) plain_layer<2, 1>(C, in, pin, out, pout, gm, rows_valid, op);
-        else plain_layer<1, 1>(C, in, pin, out, pout, gm, rows_valid, op);  // N % 64 == 0, or N = 32 (half idle)
+        if (C.N % 256 == 0) plain_layer<2, 2, T>(C, in, pin, out, pout, gm, rows_valid, op);
+        else if (C.N % 128 == 0) plain_layer<2, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);
+        else plain_layer<1, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);  // N % 64 == 0, or N = 32 (half idle)
       } else if constexpr (kWaves == 8) {
         // 8 waves (2 per SIMD, up to 256 registers each): a wave takes up to
         // four column blocks, so each A fragment feeds NB MFMAs per plane
@@ -1165,24 +1215,24 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
 #ifndef NDNET_PN_W8_NB4
 #define NDNET_PN_W8_NB4 1
 #endif
-        if (NDNET_PN_W8_NB4 && C.N % 512 == 0) plain_layer<4, 4>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 256 == 0) plain_layer<4, 2>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 128 == 0) plain_layer<4, 1>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 64 == 0) plain_layer<2, 1>(C, in, pin, out, pout, gm, rows_valid, op);
-        else plain_layer<1, 1>(C, in, pin, out, pout, gm, rows_valid, op);  // N = 32
+        if (NDNET_PN_W8_NB4 && C.N % 512 == 0) plain_layer<4, 4, T>(C, in, pin, out, pout, gm, rows_valid, op);
+        else if (C.N % 256 == 0) plain_layer<4, 2, T>(C, in, pin, out, pout, gm, rows_valid, op);
+        else if (C.N % 128 == 0) plain_layer<4, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);
+        else if (C.N % 64 == 0) plain_layer<2, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);
+        else plain_layer<1, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);  // N = 32
       } else {
 #ifndef NDNET_PN_NB2  // two column blocks per wave on the 1024-wide x6 layers (-5% per layer, r03q)
 #define NDNET_PN_NB2 1
 #endif
-        if (NDNET_PN_NB2 && C.N % 512 == 0 && C.prec) plain_layer<4, 2>(C, in, pin, out, pout, gm, rows_valid, op, pre);
-        else if (C.N % 256 == 0) plain_layer<4, 1>(C, in, pin, out, pout, gm, rows_valid, op, pre);
-        else if (C.N % 128 == 0) plain_layer<2, 1>(C, in, pin, out, pout, gm, rows_valid, op, pre);
-        else plain_layer<1, 1>(C, in, pin, out, pout, gm, rows_valid, op, pre);  // N % 64 == 0, or N = 32 (half idle)
+        if (NDNET_PN_NB2 && C.N % 512 == 0 && C.prec) plain_layer<4, 2, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);
+        else if (C.N % 256 == 0) plain_layer<4, 1, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);
+        else if (C.N % 128 == 0) plain_layer<2, 1, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);
+        else plain_layer<1, 1, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);  // N % 64 == 0, or N = 32 (half idle)
       }
     }
 #ifdef NDNET_PN_PREFETCH
     if (l + 1 < A.num_layers) {
-      prefetch_first(A, l + 1, b, pre);
+      prefetch_first<T>(A, l + 1, b, pre);
       layer_barrier();
     } else {
       __syncthreads();
@@ -1762,6 +1812,7 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
   int pw1 = 0;  // widest split-bf16 input held in region 1 (three planes of pitch K + kPadB)
   bool has_fuse = false;
   int planes = 0, qprec = 0;
+  int smode = 0;  // the one prec (1, 2 or 3) of the chain's split-bf16 layers; 0: it has none
   for (int l = 0; l < args->num_layers; l++) {
     const ndnet_pn_layer& L = args->L[l];
     if (!L.w || !L.bias || L.K <= 0 || L.K % 16 || L.N <= 0 || L.N % 32 || (L.N > 32 && L.N % 64) ||
@@ -1769,9 +1820,11 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
         L.w_cloud_stride % 4)
       PN_ARG_FAIL();
     const bool fed = l > 0 && args->L[l - 1].fuse_next;
-    if (L.prec < 0 || L.prec > 1) PN_ARG_FAIL();
+    if (L.prec < 0 || L.prec > 3) PN_ARG_FAIL();
     if (L.prec) {  // split-bf16: reads planes its producer writes (into a region, or the fused chunks)
       if (l == 0 || L.K % 32 || args->L[l - 1].N != L.K) PN_ARG_FAIL();
+      if (smode && L.prec != smode) PN_ARG_FAIL();  // one mode per chain: the kernel is instantiated per mode
+      smode = L.prec;
       if (fed) qprec = 1;
       else planes |= 1 << (l & 1);
       if (!fed && (l & 1) && L.K > pw1) pw1 = L.K;
@@ -1831,16 +1884,18 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
   }
   total = (size_t)bias_base + nbias;
   const size_t lds = sizeof(float) * total;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)k_pn_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+  const int ki = smode > 1 ? smode - 1 : 0;  // k_pn_chain<6>, <3>, <1>
+  auto* const kernel = ki == 0 ? k_pn_chain<6> : ki == 1 ? k_pn_chain<3> : k_pn_chain<1>;
+  static bool attr_set[3] = {false, false, false};
+  if (!attr_set[ki]) {
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
         hipSuccess)
       return -21;
-    attr_set = true;
+    attr_set[ki] = true;
   }
   if (lds > 160 * 1024) PN_ARG_FAIL();
   dim3 grid((args->num_points + kP - 1) / kP, batch);
-  k_pn_chain<<<grid, kThreads, lds, (hipStream_t)stream>>>(*args, planes, fbuf_off, bias_base);
+  kernel<<<grid, kThreads, lds, (hipStream_t)stream>>>(*args, planes, fbuf_off, bias_base);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     fprintf(stderr, "ndnet_amd: k_pn_chain launch failed: %s\n", hipGetErrorString(e));

@@ -215,6 +215,10 @@ class NDTNetSegmentation(nn.Module):
         self.conv4 = _conv(128, num_classes + 1)
         self.bn1, self.bn2, self.bn3 = nn.BatchNorm1d(512), nn.BatchNorm1d(256), nn.BatchNorm1d(128)
         self._hip = None  # folded-weight cache of the HIP path
+        # precision mode of this model's HIP eval forward ("x6", "x3", "bf16", "fp32":
+        # pointnet_hip.set_precision), read at every forward; None: the module-wide mode.
+        # A plain attribute: no parameter, no buffer, not in state_dict
+        self.precision = None
 
     def forward_torch(self, points: torch.Tensor, covariances: torch.Tensor) -> torch.Tensor:
         hip = _hip_train(self.conv1, self.bn1, points)

@@ -47,23 +47,43 @@ chain_timing = None
 # and NDTNet's t2-folded conv2 run as split-bf16 "x6" GEMMs
 # (include/ndnet_pointnet.h prec = 1): fp32-accurate (operands split into
 # three bf16, six exact partial products accumulated in fp32) on the bf16
-# matrix cores.  NDNET_PN_PRECISION: "x6" (default), or "fp32" to keep every
-# layer on the fp32 MFMA.  (Round 2's "x6f" -- fp32 weights split in
-# registers, measured 20-25% slower per layer -- was removed in round 3: its
-# code paths alone cost the kernel registers and scratch,
-# profiles/r03l_stamps_depth.txt.)
+# matrix cores.  NDNET_PN_PRECISION: "x6" (default), "fp32" to keep every
+# layer on the fp32 MFMA, or one of the reduced modes of the same layers, which
+# trade accuracy for matrix-core work on the same folded weights (prec 2 / 3):
+#   "x3"    three products (h h' + h m' + m h'): 16 significant bits per operand,
+#           dropped terms <= 3.02 * 2^-18 |a w| per product
+#   "bf16"  one product (h h'): plain bf16 operands, fp32 accumulation,
+#           dropped terms <= (2^-8 + 2^-18) |a w| -- autocast level
+# Measured errors and times: DESIGN.md, the section on the split-bf16 layers.
+# (Round 2's "x6f" -- fp32 weights split in registers, measured 20-25% slower
+# per layer -- was removed in round 3: its code paths alone cost the kernel
+# registers and scratch, profiles/r03l_stamps_depth.txt.  The reduced modes are
+# whole-kernel instantiations of their own and leave x6's code as it was.)
+MODES = {"x6": 1, "fp32": 1, "x3": 2, "bf16": 3}  # mode -> ndnet_pn_layer.prec of the split layers
 PRECISION = SPLIT_BF16 = X6_PREC = None
 
 
 def set_precision(mode: str) -> None:
-    """"x6" or "fp32" for models folded from now on (a model re-folds when its
-    ``_hip`` cache is cleared)."""
+    """The module-wide mode, "x6", "x3", "bf16" or "fp32": what every model
+    whose ``precision`` attribute is None runs from its next forward on (the
+    folded weights serve every mode; argument blocks are kept per mode)."""
     global PRECISION, SPLIT_BF16, X6_PREC
-    if mode not in ("x6", "fp32"):
+    if mode not in MODES:
         raise ValueError(f"unknown PointNet precision mode {mode!r}")
     PRECISION = mode
     SPLIT_BF16 = mode != "fp32"
-    X6_PREC = 1
+    X6_PREC = MODES[mode]
+
+
+def model_precision(model) -> str:
+    """The mode ``model``'s next forward runs: its ``precision`` attribute, or
+    the module-wide mode when that is None."""
+    mode = getattr(model, "precision", None)
+    if mode is None:
+        return PRECISION
+    if mode not in MODES:
+        raise ValueError(f"unknown PointNet precision mode {mode!r}")
+    return mode
 
 
 set_precision(os.environ.get("NDNET_PN_PRECISION", "x6"))
@@ -270,7 +290,10 @@ class _Folded:
             self.t1["c3"] = self.t1["c3"] + torch.eye(3, device=dev).reshape(-1)
             self.t2["c3"] = self.t2["c3"] + torch.eye(64, device=dev).reshape(-1)
         self.tensors = _tensors(m)
-        self.prec = (SPLIT_BF16, X6_NARROW)
+        # what of the precision settings the fold depends on: which layers have a split-bf16
+        # copy.  The mode itself ("x6" / "x3" / "bf16" / "fp32") does not enter: every mode
+        # reads these tensors (frag6 or frag), and the argument blocks are kept per mode
+        self.prec = (X6_NARROW,)
         self.jobs = self._fold_jobs(m)
         self._dev_jobs, self._blocks = None, 0
 
@@ -346,8 +369,9 @@ class _Folded:
         return jobs
 
     def can_refold(self, tensors) -> bool:
-        """In place: the same parameter / buffer tensors, on a GPU, at the same precision."""
-        return (self.jobs is not None and self.prec == (SPLIT_BF16, X6_NARROW) and self.c1wT.is_cuda
+        """In place: the same parameter / buffer tensors, on a GPU, with the same set of
+        split-bf16 layers (any mode: all read the one fold)."""
+        return (self.jobs is not None and self.prec == (X6_NARROW,) and self.c1wT.is_cuda
                 and len(tensors) == len(self.tensors) and all(a is b for a, b in zip(tensors, self.tensors))
                 and all(t.is_contiguous() and t.dtype == torch.float32 for t in tensors if t.is_floating_point()))
 
@@ -479,10 +503,13 @@ def _chain_torch(x: torch.Tensor, n: int, in_cols: int, layers, relus, mode: int
 
 class _Workspace:
     """Per-(batch, points) intermediates and prebuilt chain argument blocks, so
-    an eval forward does no allocation but its output and no struct building."""
+    an eval forward does no allocation but its output and no struct building.
+    The argument blocks are kept per precision mode (``structs[mode]``);
+    ``mode`` is the one ``chain`` runs, set by each forward."""
 
-    def __init__(self, W: _Folded, B: int, N: int, dev) -> None:
+    def __init__(self, W: _Folded, B: int, N: int, dev, mode: str = None) -> None:
         self.W = W
+        self.mode = PRECISION if mode is None else mode
         f32 = dict(dtype=torch.float32, device=dev)
         Fp = W.C_tail[0].shape[1]
         # the three max-pooled vectors, -inf before the atomic maxima (ReLU'd maxima are >= 0)
@@ -508,26 +535,32 @@ class _Workspace:
             (12, [(self.w1t2, self.b1t2), (W.s1aT, self.cvec)] + W.D_tail, (0, 1, 1, 1, 0), 1,
              dict(out_cols=W.C1, fuse=(1,))),
         ]
+        self.N = N
+        self.structs = {}
+
+    def hip_layers(self, mode: str) -> list:
+        """The four chains' layers for ``_build_chain`` in one precision mode:
+        every layer with a split-bf16 copy takes the mode's prec (all modes
+        read the same ``frag6``); "fp32" and the other layers read ``frag``."""
+        W = self.W
 
         def shared(wb):
             w, b = wb
-            if SPLIT_BF16 and id(w) in W.frag6:
-                return (W.frag6[id(w)], 0, b, w.shape[0], w.shape[1], X6_PREC)
+            if mode != "fp32" and id(w) in W.frag6:
+                return (W.frag6[id(w)], 0, b, w.shape[0], w.shape[1], MODES[mode])
             return (W.frag[id(w)], 0, b, w.shape[0], w.shape[1])
 
         L1 = (self.w1f, self.w1f.stride(0), W.c1b, 16, 64)
         # chain C's layer 0: conv1 with t1 and t2 folded (ndnet_pn_fold_t2_run), or
         # with t1 only and t2 folded in its prologue (NDNET_PN_FOLD_T2=chain)
         LC = (self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64) if FOLD_T2_KERNEL else L1
-        self.hip_layers = [
+        return [
             [shared(x) for x in W.A],
             [L1] + [shared(x) for x in W.B_tail],
             [LC, shared(W.C_mid), shared(W.C_tail)],
             [(self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64), shared((W.s1aT, self.cvec))] +
             [shared(x) for x in W.D_tail],
         ]
-        self.N = N
-        self.structs = None
 
     def chain(self, i: int, x: torch.Tensor, chain_fn=None, out=None) -> None:
         in_cols, layers, relus, mode, kw = self.specs[i]
@@ -537,30 +570,31 @@ class _Workspace:
                 kw["out"] = out
             chain_fn(x, self.N, in_cols, layers, relus, mode, **kw)
             return
-        if self.structs is None:
-            self.structs = [_build_chain(self.N, s[0], hl, s[2], s[3], **s[4])
-                            for s, hl in zip(self.specs, self.hip_layers)]
+        structs = self.structs.get(self.mode)
+        if structs is None:
+            structs = self.structs[self.mode] = [_build_chain(self.N, s[0], hl, s[2], s[3], **s[4])
+                                                 for s, hl in zip(self.specs, self.hip_layers(self.mode))]
             # the last chain re-arms the max-pool buffer (-inf) for the next forward
-            self.structs[3].clear = self.gbuf.data_ptr()
-            self.structs[3].clear_count = self.gbuf.numel()
+            structs[3].clear = self.gbuf.data_ptr()
+            structs[3].clear_count = self.gbuf.numel()
             if HEAD3_IN_CHAIN:  # chain B computes t1 and its conv1 weights itself
-                W, cb = self.W, self.structs[1]
+                W, cb = self.W, structs[1]
                 cb.head_h2, cb.head_ld, cb.head_K = self.h2.data_ptr(), self.h2.stride(0), self.h2.shape[1]
                 cb.head_w3, cb.head_b3 = W.t1["f3"].data_ptr(), W.t1["c3"].data_ptr()
                 cb.head_basis, cb.head_kin, cb.head_nout = W.t1_basis.data_ptr(), 12, 64
                 cb.head_t1 = self.t1.data_ptr()
             if not FOLD_T2_KERNEL:  # chain C: t2 through layer 0 (prologue fold), published for chain D
-                cc = self.structs[2]
+                cc = structs[2]
                 cc.fold_t2, cc.fold_ld = self.t2.data_ptr(), self.t2.stride(0)
                 cc.fold_out_w, cc.fold_out_b = self.w1t2f.data_ptr(), self.b1t2.data_ptr()
         if chain_timing is not None:  # torch events on the launch stream (bench.py)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            _run_chain(self.structs[i], x, out)
+            _run_chain(structs[i], x, out)
             e1.record()
             chain_timing.append((i, e0, e1))
         else:
-            _run_chain(self.structs[i], x, out)
+            _run_chain(structs[i], x, out)
 
 
 def _folded(model):
@@ -714,10 +748,12 @@ class workspace_slot:
 def segmentation_forward(model, points: torch.Tensor, covariances: torch.Tensor, chain=None) -> torch.Tensor:
     """model(points [B,N,3], covariances [B,N,9]) -> log-probs [B,N,C+1], eval mode.
 
-    ``chain``: None runs every step on the HIP kernels; a chain emulator
+    The split-bf16 layers run in the model's precision mode as of this call
+    (``model_precision``).  ``chain``: None runs every step on the HIP kernels; a chain emulator
     (``_chain_torch``) runs the chains and the per-cloud steps as torch ops.
     Concurrent forwards (different streams, no order) need different
     ``workspace_slot``s."""
+    mode = model_precision(model)
     cache = _folded(model)
     W = cache["W"]
     B, N, _ = points.shape
@@ -725,7 +761,8 @@ def segmentation_forward(model, points: torch.Tensor, covariances: torch.Tensor,
     key = (B, N, dev, _slot)
     ws = cache["ws"].get(key)
     if ws is None:
-        ws = cache["ws"][key] = _Workspace(W, B, N, dev)
+        ws = cache["ws"][key] = _Workspace(W, B, N, dev, mode)
+    ws.mode = mode  # the model's mode as of this forward: its argument blocks are kept per mode
     # one [B,N,12] block; ndt_preprocessing already returns views of one
     if (points.stride() == (N * 12, 12, 1) and covariances.stride() == (N * 12, 12, 1)
             and covariances.data_ptr() == points.data_ptr() + 12 and points.dtype == torch.float32):

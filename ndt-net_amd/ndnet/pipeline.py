@@ -129,6 +129,12 @@ class GraphedSegmentation:
     ``points`` is the static float32 input buffer; ``__call__(new_points)``
     copies into it, replays, and returns the static ``[B, num_nds, C+1]``
     output buffer (overwritten by the next replay -- clone to keep it).
+
+    The graph keeps the precision mode it was captured with
+    (``model.precision`` or ``pointnet_hip.PRECISION`` at construction): the
+    mode selects the kernels and argument blocks the capture recorded, so a
+    later change of either shows in eager forwards only; build a new graph
+    for another mode.
     """
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,
@@ -214,6 +220,10 @@ class PipelinedSegmentation:
     ``levels`` (config C5): the NDT stage is ndt_multiscale (downsample to
     levels[0], prune to each further level) and the forward stage one forward
     per level; the output is then the list of per-level log-probs.
+
+    The forward graphs keep the precision mode they were captured with
+    (``model.precision`` or ``pointnet_hip.PRECISION`` at construction), as
+    ``GraphedSegmentation`` does.
     """
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,
