@@ -8,7 +8,8 @@
  * :233-241 (segmentation head), each of which the reference runs as separate
  * torch ops with activations round-tripping through memory.  Host side:
  * ndt-net_amd/ndnet/models/pointnet_hip.py (BatchNorm folding, per-cloud
- * steps, the four chains A-D).
+ * steps, the four chains A-D).  NDTNetClassification's eval forward shares
+ * chains A-C and ends in its own head (ndnet_pn_cls_head_run below).
  *
  * Layer weights are W^T (K input channels x N output channels) with BatchNorm
  * folded in, K padded to a multiple of 16 and N to 32 (N <= 32) or 64, stored FRAGMENT-MAJOR
@@ -139,6 +140,29 @@ int ndnet_pn_fc_run(const float *in, int ld_in, const float *W, const float *bia
  * workgroups, each summing its waves' K-slices in a fixed order. */
 int ndnet_pn_fc_mfma_run(const float *in, int ld_in, const float *Wf, const float *bias, float *out, int ld_out,
                          int batch, int K, int N, int relu, void *stream);
+/* The classification head's last layer and softmax (ndtnet.py:188-194: conv3
+ * then softmax over the classes; no BatchNorm) in one launch, for any batch:
+ *   probs[b][c] = softmax_c(bias[c] + sum_k in[b][k] W^T[k][c]),  c < out_cols
+ * Wf = W^T fragment-major as for ndnet_pn_fc_mfma_run (K x N, prec-0 layout),
+ * K % 16 == 0, K <= 256, N % 16 == 0, N <= 1024, 1 <= out_cols <= N (columns
+ * at or past out_cols are padding: computed, never part of the maximum or the
+ * sum, never written), batch >= 1; in and Wf 16-byte aligned, ld_in % 4 == 0,
+ * ld_in >= K, ld_probs >= out_cols (and ld_logits >= out_cols with logits).
+ * One workgroup per 16 clouds, ceil(batch / 16) of them, none waiting for
+ * another; the 16 x N logits stay in LDS, a column's K-sum is formed by one
+ * wave in a fixed order (bit-identical from run to run), the exponential is
+ * the accurate expf of x - max and the division a true one.
+ *   logits  optional (NULL: not written): the pre-softmax values, [batch][ld_logits]
+ *   clear   optional (NULL with clear_count 0): clear[0 .. clear_count) is set
+ *           to -inf, the workgroups sharing the range -- re-arms the max-pool
+ *           buffer for the next forward.  The kernel reads nothing of it, so
+ *           it must not overlap in, Wf or bias; its last reader must be
+ *           earlier in stream order.
+ * Same return codes as ndnet_pn_chain_run (-20 before any launch, -21 on a
+ * launch failure); no allocation, no synchronisation: graph-capturable. */
+int ndnet_pn_cls_head_run(const float *in, int ld_in, const float *Wf, const float *bias, float *probs,
+                          int ld_probs, float *logits, int ld_logits, int batch, int K, int N, int out_cols,
+                          float *clear, int64_t clear_count, void *stream);
 /* BatchNorm fold of the eval forward's weights, re-run in place after a
  * weight update (the host-side first fold: pointnet_hip._Folded; the folds
  * it restates: ndtnet.py's Conv1d / Linear + BatchNorm1d pairs, :45-60,

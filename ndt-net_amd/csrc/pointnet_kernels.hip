@@ -1392,6 +1392,91 @@ __global__ void __launch_bounds__(kFcWaves * 64) k_pn_fc_mfma(const float* __res
   }
 }
 
+#if NDNET_PN_TILE == 64
+// The classification head's last layer and its softmax (ndtnet.py:188-194) in
+// one launch: probs[b] = softmax(in[b] @ W^T + bias) over the first out_cols
+// of N padded columns.  One workgroup per chunk of 16 clouds (one 16-row tile
+// of the fp32 MFMA); no workgroup talks to another.  Every wave keeps the
+// chunk's 16 x K input fragment in registers (K <= 256: 16 float4) and
+// streams the weight fragments of its column blocks (wave, wave + 8, ...),
+// the next block's loads issued ahead of the current one's MFMAs (as compiled
+// they are waited for before the chain; a straight-line variant that keeps
+// them in flight across it measured slower, 24.4 against 19.6 us at N = 512);
+// one wave forms a column's whole K-sum, k-group by k-group, so the result
+// does not depend on scheduling.  The 16 x N logits (+ bias) go to LDS (<= 64 KB) and
+// never to memory unless `logits` asks for them; then one wave per row takes
+// the maximum of the first out_cols columns (padded columns take no part),
+// exp(x - max) with the accurate expf, the sum (64 strided partial sums, then a
+// butterfly) and a true division.  Rows at or past `batch` read the chunk's
+// first row and are discarded.  `clear` is filled with -inf, the workgroups
+// sharing the range: the kernel does not read it.
+constexpr int kClsWaves = 8, kClsMaxG = 16;  // K <= 16 * kClsMaxG = 256
+__global__ void __launch_bounds__(kClsWaves * 64) k_pn_cls_head(const float* __restrict__ in, int ld_in,
+                                                                const f32x4* __restrict__ wf,
+                                                                const float* __restrict__ bias, float* __restrict__ probs,
+                                                                int ld_probs, float* __restrict__ logits, int ld_logits,
+                                                                int batch, int KG, int N, int out_cols,
+                                                                float* __restrict__ clear, int64_t clear_count) {
+  extern __shared__ float cls_lg[];  // [16][N]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int kq = lane >> 4, cl = lane & 15;
+  for (int64_t i = (int64_t)blockIdx.x * (kClsWaves * 64) + threadIdx.x; i < clear_count;
+       i += (int64_t)gridDim.x * (kClsWaves * 64))
+    clear[i] = -INFINITY;
+  const int b0 = blockIdx.x * 16;
+  const int B = batch - b0 < 16 ? batch - b0 : 16;
+  const float* xr = in + (int64_t)(b0 + (cl < B ? cl : 0)) * ld_in + 4 * kq;
+  f32x4 xv[kClsMaxG], cur[kClsMaxG], nxt[kClsMaxG];
+#pragma unroll
+  for (int i = 0; i < kClsMaxG; i++)
+    if (i < KG) xv[i] = *reinterpret_cast<const f32x4*>(xr + 16 * i);
+  const int nb = N >> 4;
+  if (wave < nb) {
+#pragma unroll
+    for (int i = 0; i < kClsMaxG; i++)
+      if (i < KG) cur[i] = wf[((int64_t)wave * KG + i) * 64 + lane];
+  }
+  for (int cb = wave; cb < nb; cb += kClsWaves) {
+    if (cb + kClsWaves < nb) {
+#pragma unroll
+      for (int i = 0; i < kClsMaxG; i++)
+        if (i < KG) nxt[i] = wf[((int64_t)(cb + kClsWaves) * KG + i) * 64 + lane];
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < kClsMaxG; i++)
+      if (i < KG)
+#pragma unroll
+        for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[i][s], cur[i][s], acc, 0, 0, 0);
+    // lane (kq, cl): clouds 4 kq + r of column 16 cb + cl
+    const int n = 16 * cb + cl;
+    const float bv = bias[n];
+#pragma unroll
+    for (int r = 0; r < 4; r++) cls_lg[(4 * kq + r) * N + n] = acc[r] + bv;
+#pragma unroll
+    for (int i = 0; i < kClsMaxG; i++) cur[i] = nxt[i];
+  }
+  __syncthreads();
+  for (int r = wave; r < B; r += kClsWaves) {  // one wave per cloud; a lane rereads only what it wrote
+    float* row = cls_lg + r * N;
+    float m = -INFINITY;
+    for (int c = lane; c < out_cols; c += 64) m = fmaxf(m, row[c]);
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    float sum = 0.0f;
+    for (int c = lane; c < out_cols; c += 64) {
+      const float x = row[c];
+      if (logits) logits[(int64_t)(b0 + r) * ld_logits + c] = x;
+      const float e = expf(x - m);
+      row[c] = e;
+      sum += e;
+    }
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    float* pr = probs + (int64_t)(b0 + r) * ld_probs;
+    for (int c = lane; c < out_cols; c += 64) pr[c] = row[c] / sum;
+  }
+}
+#endif
+
 // Index of W^T element (k, n) in the fragment-major layout (KG k-groups).
 __device__ inline int64_t frag_index(int k, int n, int KG) {
   return ((int64_t)((n >> 4) * KG + (k >> 4)) * 64 + ((k >> 2) & 3) * 16 + (n & 15)) * 4 + (k & 3);
@@ -1697,6 +1782,20 @@ int ndnet_pn_fc_mfma_run(const float* in, int ld_in, const float* Wf, const floa
     k_pn_fc_mfma<2><<<nb / 2, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, out, ld_out, batch, KG, relu);
   else
     k_pn_fc_mfma<1><<<nb, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, out, ld_out, batch, KG, relu);
+  return hipGetLastError() == hipSuccess ? 0 : -21;
+}
+
+int ndnet_pn_cls_head_run(const float* in, int ld_in, const float* Wf, const float* bias, float* probs, int ld_probs,
+                          float* logits, int ld_logits, int batch, int K, int N, int out_cols, float* clear,
+                          int64_t clear_count, void* stream) {
+  if (!in || !Wf || !bias || !probs || batch <= 0 || K <= 0 || K % 16 || K > 16 * kClsMaxG || N <= 0 || N % 16 ||
+      N > 1024 || out_cols < 1 || out_cols > N || ld_in % 4 || ld_in < K || ld_probs < out_cols ||
+      (logits && ld_logits < out_cols) || ((uintptr_t)in | (uintptr_t)Wf) % 16 || clear_count < 0 ||
+      (!clear && clear_count))
+    return -20;
+  k_pn_cls_head<<<(batch + 15) / 16, kClsWaves * 64, (size_t)16 * N * sizeof(float), (hipStream_t)stream>>>(
+      in, ld_in, reinterpret_cast<const f32x4*>(Wf), bias, probs, ld_probs, logits, ld_logits, batch, K / 16, N,
+      out_cols, clear, clear_count);
   return hipGetLastError() == hipSuccess ? 0 : -21;
 }
 

@@ -128,6 +128,7 @@ POINTNET_EXPORTS: dict = {
     "ndnet_ply_read": (_I, [ctypes.c_char_p, _I, _I, _P, _P, _U64, ctypes.POINTER(_U64), _I]),
     "ndnet_pn_fc_run": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ndnet_pn_fc_mfma_run": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ndnet_pn_cls_head_run": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, ctypes.c_int64, _P]),
     "ndnet_pn_head3_run": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ndnet_pn_fold_t2_run": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _P]),
     "ndnet_pn_fold_prepare": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64)]),

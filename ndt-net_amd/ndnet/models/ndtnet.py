@@ -8,8 +8,11 @@ Module tree and parameter names follow the reference
       feature_extractor: NDTNet
         conv1/conv2/conv3 (+bn1..3), t1: TNet(3), t2: TNet(64)
       conv1..conv4, bn1..bn3
+    NDTNetClassification
+      feature_extractor: NDTNet
+      conv1..conv3
 
-Two forward paths:
+Forward paths (the eval path for both models, the train path for segmentation):
   * eval mode on a gfx950 GPU with no autograd wanted (``torch.no_grad()``,
     or nothing requires grad) -> the fused HIP kernels of
     lib/libndnet_amd.so (``ndnet.models.pointnet_hip``): BatchNorm folded into
@@ -185,24 +188,72 @@ class NDTNet(nn.Module):
         return x, x_t2
 
 
-class NDTNetClassification(nn.Module):
-    """Global classifier head (reference ndtnet.py:166-196)."""
+class _HipEval:
+    """What the two models share around their HIP eval forward
+    (``ndnet.models.pointnet_hip``): the folded-weight cache, the precision
+    attribute, the dispatch rule and the stale mark of a mode change."""
+
+    def _init_hip(self) -> None:
+        self._hip = None  # folded-weight cache of the HIP path
+        # precision mode of this model's HIP eval forward ("x6", "x3", "bf16", "fp32":
+        # pointnet_hip.set_precision), read at every forward; None: the module-wide mode.
+        # A plain attribute: no parameter, no buffer, not in state_dict
+        self.precision = None
+
+    def _needs_autograd(self, points: torch.Tensor, covariances: torch.Tensor) -> bool:
+        """The reference forward is differentiable in eval mode too (frozen-BN
+        fine-tuning, saliency): with grad enabled and anything requiring grad,
+        the autograd composition runs, not the inference kernels."""
+        if not torch.is_grad_enabled():
+            return False
+        return points.requires_grad or covariances.requires_grad or any(p.requires_grad for p in self.parameters())
+
+    def _hip_eval(self, points: torch.Tensor, covariances: torch.Tensor) -> bool:
+        """Eval mode on a cuda device with no autograd wanted: the HIP path, for
+        the widths its kernels take."""
+        return (not self.training and points.is_cuda and self.point_dim == 3
+                and not self._needs_autograd(points, covariances))
+
+    def train(self, mode: bool = True):
+        # a mode change: weights may change (also inside a replayed training
+        # graph, which bumps no tensor versions), so the next eval forward
+        # re-folds -- in place, one ndnet_pn_fold_run launch
+        # (pointnet_hip._folded); a redundant eval() keeps the fold
+        if bool(mode) != self.training and self._hip is not None:
+            self._hip["stale"] = True
+        return super().train(mode)
+
+
+class NDTNetClassification(_HipEval, nn.Module):
+    """Global classifier head (reference ndtnet.py:166-196): class
+    probabilities [B, num_classes, 1]."""
 
     def __init__(self, point_dim: int = 3, num_classes: int = 512, feature_dim: int = 768) -> None:
         super().__init__()
         self.point_dim, self.num_classes, self.feature_dim = point_dim, num_classes, feature_dim
         self.feature_extractor = NDTNet(point_dim, feature_dim=feature_dim)
         self.conv1, self.conv2, self.conv3 = _conv(feature_dim, 512), _conv(512, 256), _conv(256, num_classes)
+        self._init_hip()
 
-    def forward(self, points: torch.Tensor, covariances: torch.Tensor) -> torch.Tensor:
+    def forward_torch(self, points: torch.Tensor, covariances: torch.Tensor) -> torch.Tensor:
         x, _ = self.feature_extractor(points, covariances)
         x = x.amax(dim=2, keepdim=True)
         x = torch.relu(self.conv1(x))
         x = torch.relu(self.conv2(x))
         return torch.softmax(self.conv3(x), dim=1)
 
+    def forward(self, points: torch.Tensor, covariances: torch.Tensor) -> torch.Tensor:
+        if self._hip_eval(points, covariances):
+            # as NDTNetSegmentation.forward: a cuda eval forward IS the HIP path; only widths
+            # the kernels do not take (pointnet_hip.supports_classification: feature_dim or
+            # num_classes above 1024) run the torch composition
+            from . import pointnet_hip
+            if pointnet_hip.supports_classification(self):
+                return pointnet_hip.classification_forward(self, points, covariances)
+        return self.forward_torch(points, covariances)
 
-class NDTNetSegmentation(nn.Module):
+
+class NDTNetSegmentation(_HipEval, nn.Module):
     """Per-ND segmentation (reference ndtnet.py:198-243): log-probs [B,N,C+1]."""
 
     def __init__(self, point_dim: int = 3, num_classes: int = 16, feature_dim: int = 1024) -> None:
@@ -214,11 +265,7 @@ class NDTNetSegmentation(nn.Module):
         self.conv3 = _conv(256, 128)
         self.conv4 = _conv(128, num_classes + 1)
         self.bn1, self.bn2, self.bn3 = nn.BatchNorm1d(512), nn.BatchNorm1d(256), nn.BatchNorm1d(128)
-        self._hip = None  # folded-weight cache of the HIP path
-        # precision mode of this model's HIP eval forward ("x6", "x3", "bf16", "fp32":
-        # pointnet_hip.set_precision), read at every forward; None: the module-wide mode.
-        # A plain attribute: no parameter, no buffer, not in state_dict
-        self.precision = None
+        self._init_hip()
 
     def forward_torch(self, points: torch.Tensor, covariances: torch.Tensor) -> torch.Tensor:
         hip = _hip_train(self.conv1, self.bn1, points)
@@ -244,17 +291,8 @@ class NDTNetSegmentation(nn.Module):
             x = torch.nn.functional.log_softmax(x, dim=1)
         return x.transpose(2, 1)
 
-    def _needs_autograd(self, points: torch.Tensor, covariances: torch.Tensor) -> bool:
-        """The reference forward is differentiable in eval mode too (frozen-BN
-        fine-tuning, saliency): with grad enabled and anything requiring grad,
-        the autograd composition runs, not the inference kernels."""
-        if not torch.is_grad_enabled():
-            return False
-        return points.requires_grad or covariances.requires_grad or any(p.requires_grad for p in self.parameters())
-
     def forward(self, points: torch.Tensor, covariances: torch.Tensor) -> torch.Tensor:
-        if (not self.training and points.is_cuda and self.point_dim == 3
-                and not self._needs_autograd(points, covariances)):
+        if self._hip_eval(points, covariances):
             # a cuda eval forward IS the HIP path: a missing library raises
             # (ndnet._lib.lib()) instead of silently running the torch composition.
             # Only widths the kernels do not take (pointnet_hip.supports: feature_dim
@@ -264,12 +302,3 @@ class NDTNetSegmentation(nn.Module):
             if pointnet_hip.supports(self):
                 return pointnet_hip.segmentation_forward(self, points, covariances)
         return self.forward_torch(points, covariances)
-
-    def train(self, mode: bool = True):
-        # a mode change: weights may change (also inside a replayed training
-        # graph, which bumps no tensor versions), so the next eval forward
-        # re-folds -- in place, one ndnet_pn_fold_run launch
-        # (pointnet_hip._folded); a redundant eval() keeps the fold
-        if bool(mode) != self.training and self._hip is not None:
-            self._hip["stale"] = True
-        return super().train(mode)

@@ -24,6 +24,14 @@ per-cloud steps (TNet FC heads and the seg head's global-feature bias on the
 fp32 MFMA, ``ndnet_pn_fc_mfma_run``; the t1 / t2 weight folds) are HIP
 kernels on the same stream (``_glue_hip``); ``_glue_torch`` is their torch
 restatement for the tests.
+
+NDTNetClassification (``classification_forward``) shares chains A-C, the
+per-cloud steps, the fold and the workspace; instead of D its head
+(ndtnet.py:188-194, no BatchNorm) runs on the pooled g3 per cloud:
+relu(conv1: F -> 512) and relu(conv2: 512 -> 256) as two
+``ndnet_pn_fc_mfma_run`` launches, then conv3 (256 -> num_classes) and the
+softmax in one ``ndnet_pn_cls_head_run``, which also re-arms the max-pool
+buffer -> probabilities [B, num_classes, 1].
 """
 from __future__ import annotations
 
@@ -103,7 +111,17 @@ X6_NARROW = os.environ.get("NDNET_PN_X6_NARROW", "1") == "1"
 # 160 KB hold.  A model outside these runs ndtnet's torch composition.
 MAX_FEATURE_DIM = 1024
 MAX_LAST_N = 448
+MAX_CLASSES = 1024  # NDTNetClassification: ndnet_pn_cls_head_run's padded N
 X6_LAST_MAX_N = 64  # 128 -> C+1 as a split-bf16 layer up to this padded width (_Folded)
+
+
+def supports_classification(model) -> bool:
+    """The same for an ``NDTNetClassification``: its head's conv1 is one
+    ndnet_pn_fc_mfma_run with K = F (<= 1024), and ndnet_pn_cls_head_run keeps
+    a 16-cloud chunk's logits in LDS (16 x 1024 floats: num_classes <= 1024)."""
+    F = model.feature_dim
+    return (1 <= F <= MAX_FEATURE_DIM and (FC_MFMA or F % 4 == 0) and 1 <= model.num_classes <= MAX_CLASSES
+            and model.point_dim == 3)
 
 
 def supports(model) -> bool:
@@ -224,17 +242,15 @@ class _Folded:
                 return dict(w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3, f1=f1, c1=c1, f2=f2, c2=c2,
                             f3=t.fc3.weight.float(), c3=t.fc3.bias.float())
 
+            self.seg = hasattr(m, "conv4")  # NDTNetSegmentation; else NDTNetClassification (no BatchNorm in its head)
+            F = m.feature_dim
+            self.F = F
+            # ---- the feature extractor (chains A-C), the same for either model ----
             self.t1 = tnet(fe.t1)
             self.t2 = tnet(fe.t2)
             self.c1w, self.c1b = conv(fe.conv1, fe.bn1)   # [64, 12]
             self.c2w, self.c2b = conv(fe.conv2, fe.bn2)   # [128, 64]
             self.c3w, self.c3b = conv(fe.conv3, fe.bn3)   # [F, 128]
-            self.s1w, self.s1b = conv(m.conv1, m.bn1)     # [512, 64 + F]
-            self.s2w, self.s2b = conv(m.conv2, m.bn2)
-            self.s3w, self.s3b = conv(m.conv3, m.bn3)
-            self.s4w, self.s4b = m.conv4.weight[:, :, 0].float(), m.conv4.bias.float()
-            F = m.feature_dim
-            self.F, self.C1 = F, m.num_classes + 1
             # shared per-point layers, W^T padded
             t1, t2 = self.t1, self.t2
             self.A = [(_wT(t1["w1"], 16, 64), t1["b1"]), (_wT(t1["w2"], 64, 128), t1["b2"]),
@@ -242,17 +258,11 @@ class _Folded:
             self.B_tail = [(_wT(t2["w1"], 64, 64), t2["b1"]), (_wT(t2["w2"], 64, 128), t2["b2"]),
                            (_wT(t2["w3"], 128, 1024), t2["b3"])]
             self.C_tail = (_wT(self.c3w, 128, _npad(F)), _bpad(self.c3b, _npad(F)))
-            self.s1a = self.s1w[:, :64].contiguous()      # acts on x_t2
-            self.s1bT = self.s1w[:, 64:].t().contiguous()  # [F, 512], acts on g3
-            self.s1g = self.s1w[:, 64:].contiguous()       # [512, F] row-major for ndnet_pn_fc_run
-            self.D_tail = [(_wT(self.s2w, 512, 256), self.s2b), (_wT(self.s3w, 256, 128), self.s3b),
-                           (_wT(self.s4w, 128, _npad(self.C1)), _bpad(self.s4b, _npad(self.C1)))]
             self.c1wT = self.c1w.t().contiguous()         # [12, 64]
             # x_t2 = t2^T x1 (ndtnet.py:152-157) feeds conv2 and the seg head's
             # conv1a; t2 is folded into chains C / D's layer 0 (their prologue,
             # ndnet_pn_chain.fold_t2), so both layers keep shared weights
             self.C_mid = (_wT(self.c2w, 64, 128), self.c2b)          # conv2 W^T [64, 128]
-            self.s1aT = _wT(self.s1a, 64, 512)                        # seg conv1a W^T [64, 512]
             # conv1 of the t1-transformed input: (W1 M(t1))^T = sum_ac t1[a,c] E_ac^T W1^T,
             # M(t1) = blockdiag(t1, kron(t1, I3)) (p' = t1 p, C' = t1 C)
             dev = self.c1wT.device
@@ -263,29 +273,35 @@ class _Folded:
                     for j in range(3):
                         E[3 * a + c, 3 + 3 * a + j, 3 + 3 * c + j] = 1.0
             self.t1_basis = torch.matmul(E.transpose(1, 2), self.c1wT).reshape(9, 12 * 64).contiguous()
-            # fragment-major copies of the shared per-point layers (the HIP chains)
-            self.frag = {id(w): _frag(w) for w, _ in
-                         self.A + self.B_tail + [self.C_mid, self.C_tail, (self.s1aT, None)] + self.D_tail}
-            # the wide pooled layers, conv2 and the seg head's conv1a in split-bf16 form
-            self.wide = [self.A[2][0], self.B_tail[2][0], self.C_tail[0], self.D_tail[0][0], self.D_tail[1][0],
-                         self.C_mid[0], self.s1aT]
+            # the per-point layers with fragment-major copies (the HIP chains) ...
+            self.chain_w = [w for w, _ in self.A + self.B_tail + [self.C_mid, self.C_tail]]
+            # ... and the wide pooled layers and conv2 in split-bf16 form
+            self.wide = [self.A[2][0], self.B_tail[2][0], self.C_tail[0]]
+            # the FC layers of the TNet heads, W^T fragment-major for the MFMA GEMV (ndnet_pn_fc_mfma_run)
+            self.fcs = [self.t1["f1"], self.t1["f2"], self.t2["f1"], self.t2["f2"], self.t2["f3"]]
+            if self.seg:
+                self._fold_seg(m, conv)
+            else:
+                self._fold_cls(m)
+            self.wide.append(self.C_mid[0])
+            if self.seg:
+                self.wide.append(self.s1aT)
             if X6_NARROW:  # the K >= 64 fp32-MFMA layers too (64 -> 128 of TNet(3) / TNet(64), 64 -> 64, 128 -> C+1)
                 self.wide += [self.A[1][0], self.B_tail[0][0], self.B_tail[1][0]]
                 # 128 -> C+1 only up to 64 padded columns: as a split-bf16 layer its input is three
                 # 128-wide bf16 planes (54 KB in the 64-point build) next to chain D's 256-wide
                 # planes (102 KB), which with the biases fills the 160 KB of LDS at N = 64 exactly;
                 # a wider last layer reads fp32 rows (34 KB)
-                if self.D_tail[2][0].shape[1] <= X6_LAST_MAX_N:
+                if self.seg and self.D_tail[2][0].shape[1] <= X6_LAST_MAX_N:
                     self.wide.append(self.D_tail[2][0])
+            self.frag = {id(w): _frag(w) for w in self.chain_w}
             self.frag6 = {id(w): _frag_x6(w) for w in self.wide}
-            # the FC layers of the TNet heads and the seg head's global-feature
-            # bias, W^T fragment-major for the MFMA GEMV (ndnet_pn_fc_mfma_run);
-            # the latter's K = F padded to a multiple of 16 with zero rows: the
-            # layer then reads g3's padded columns, which chain C leaves at 0
+            # a layer whose K is a model width (the seg head's global-feature bias, the
+            # classification head's conv1: K = F) has it padded to a multiple of 16 with
+            # zero rows: the layer then reads g3's padded columns, which chain C leaves at 0
             # (zero weight columns and bias, no ReLU)
-            self.fcf = {id(w): _frag(w.t().contiguous()) for w in
-                        (self.t1["f1"], self.t1["f2"], self.t2["f1"], self.t2["f2"], self.t2["f3"])}
-            self.fcf[id(self.s1g)] = _frag(_wT(self.s1g, _pad(F, 16), 512))
+            self.fcf = {id(w): _frag(_wT(w.reshape(w.shape[0], -1), _pad(w.shape[1], 16), w.shape[0]))
+                        for w in self.fcs}
             # the identity the TNet heads add (ndtnet.py:59), folded into fc3's bias
             self.t1["c3"] = self.t1["c3"] + torch.eye(3, device=dev).reshape(-1)
             self.t2["c3"] = self.t2["c3"] + torch.eye(64, device=dev).reshape(-1)
@@ -296,6 +312,41 @@ class _Folded:
         self.prec = (X6_NARROW,)
         self.jobs = self._fold_jobs(m)
         self._dev_jobs, self._blocks = None, 0
+
+    def _fold_seg(self, m, conv) -> None:
+        """The segmentation head (chain D and its global-feature bias)."""
+        F = self.F
+        self.C1 = m.num_classes + 1
+        self.s1w, self.s1b = conv(m.conv1, m.bn1)     # [512, 64 + F]
+        self.s2w, self.s2b = conv(m.conv2, m.bn2)
+        self.s3w, self.s3b = conv(m.conv3, m.bn3)
+        self.s4w, self.s4b = m.conv4.weight[:, :, 0].float(), m.conv4.bias.float()
+        self.s1a = self.s1w[:, :64].contiguous()      # acts on x_t2
+        self.s1bT = self.s1w[:, 64:].t().contiguous()  # [F, 512], acts on g3
+        self.s1g = self.s1w[:, 64:].contiguous()       # [512, F] row-major for ndnet_pn_fc_run
+        self.D_tail = [(_wT(self.s2w, 512, 256), self.s2b), (_wT(self.s3w, 256, 128), self.s3b),
+                       (_wT(self.s4w, 128, _npad(self.C1)), _bpad(self.s4b, _npad(self.C1)))]
+        self.s1aT = _wT(self.s1a, 64, 512)                        # seg conv1a W^T [64, 512]
+        self.chain_w += [self.s1aT] + [w for w, _ in self.D_tail]
+        self.wide += [self.D_tail[0][0], self.D_tail[1][0]]
+        self.fcs.append(self.s1g)
+
+    def _fold_cls(self, m) -> None:
+        """The classification head (ndtnet.py:188-194: conv1, conv2 with ReLU,
+        conv3, softmax; no BatchNorm): conv1 / conv2 as FC layers of
+        ndnet_pn_fc_mfma_run, conv3 W^T fragment-major with the classes padded
+        to 16 columns for ndnet_pn_cls_head_run, its bias padded with zeros.
+        The rows and biases are the parameters themselves ([N, K, 1], as fc3's;
+        no view of one is kept: a view made under no_grad breaks a later
+        deepcopy of the model once its base has been updated in place)."""
+        self.C = m.num_classes
+        self.h1w, self.h1b = m.conv1.weight.float(), m.conv1.bias.float()   # [512, F, 1]
+        self.h2w, self.h2b = m.conv2.weight.float(), m.conv2.bias.float()   # [256, 512, 1]
+        self.h3w = m.conv3.weight.float()                                   # [C, 256, 1]
+        self.Cp = _pad(self.C, 16)
+        self.h3f = _frag(_wT(self.h3w[:, :, 0], 256, self.Cp))
+        self.h3b = _bpad(m.conv3.bias.float(), self.Cp)
+        self.fcs += [self.h1w, self.h2w]
 
     def _fold_jobs(self, m) -> list:
         """The recipe of every tensor above as ndnet_pn_fold_job fields (kind,
@@ -334,38 +385,48 @@ class _Folded:
             bias(t["c2"], tm.fc2, tm.bn5)
             bias(t["c3"], tm.fc3, None, eye=d)
             src[id(t["f3"])] = (tm.fc3, None, 0, tm.fc3.weight.shape[1])  # the parameter itself
-        for (w, b), conv, bn in (((self.c1w, self.c1b), fe.conv1, fe.bn1), ((self.c2w, self.c2b), fe.conv2, fe.bn2),
-                                 ((self.c3w, self.c3b), fe.conv3, fe.bn3), ((self.s1w, self.s1b), m.conv1, m.bn1),
-                                 ((self.s2w, self.s2b), m.conv2, m.bn2), ((self.s3w, self.s3b), m.conv3, m.bn3)):
+        convs = [((self.c1w, self.c1b), fe.conv1, fe.bn1), ((self.c2w, self.c2b), fe.conv2, fe.bn2),
+                 ((self.c3w, self.c3b), fe.conv3, fe.bn3)]
+        if self.seg:
+            convs += [((self.s1w, self.s1b), m.conv1, m.bn1), ((self.s2w, self.s2b), m.conv2, m.bn2),
+                      ((self.s3w, self.s3b), m.conv3, m.bn3)]
+        for (w, b), conv, bn in convs:
             rows(w, conv, bn)
             bias(b, conv, bn)
-        rows(self.s1a, m.conv1, m.bn1, 0, 64)
-        rows(self.s1g, m.conv1, m.bn1, 64, self.F)
-        wt(self.s1bT, m.conv1, m.bn1, 64, self.F)
+        if self.seg:
+            rows(self.s1a, m.conv1, m.bn1, 0, 64)
+            rows(self.s1g, m.conv1, m.bn1, 64, self.F)
+            wt(self.s1bT, m.conv1, m.bn1, 64, self.F)
         for layers, tm in ((self.A, fe.t1), (self.B_tail, fe.t2)):
             for i, (w, _) in enumerate(layers, 1):
                 wt(w, getattr(tm, f"conv{i}"), getattr(tm, f"bn{i}"))
         wt(self.C_tail[0], fe.conv3, fe.bn3)
         bias(self.C_tail[1], fe.conv3, fe.bn3)
-        wt(self.D_tail[0][0], m.conv2, m.bn2)
-        wt(self.D_tail[1][0], m.conv3, m.bn3)
-        wt(self.D_tail[2][0], m.conv4, None)
-        bias(self.D_tail[2][1], m.conv4, None)
+        if self.seg:
+            wt(self.D_tail[0][0], m.conv2, m.bn2)
+            wt(self.D_tail[1][0], m.conv3, m.bn3)
+            wt(self.D_tail[2][0], m.conv4, None)
+            bias(self.D_tail[2][1], m.conv4, None)
         wt(self.c1wT, fe.conv1, fe.bn1)
         wt(self.C_mid[0], fe.conv2, fe.bn2)
-        wt(self.s1aT, m.conv1, m.bn1, 0, 64)
+        if self.seg:
+            wt(self.s1aT, m.conv1, m.bn1, 0, 64)
+        else:  # the head's conv1 / conv2 rows are the parameters themselves (no BatchNorm)
+            src[id(self.h1w)] = (m.conv1, None, 0, self.F)
+            src[id(self.h2w)] = (m.conv2, None, 0, 512)
         add(4, self.t1_basis, fe.conv1, fe.bn1)
-        wts = {id(w): w for w, _ in self.A + self.B_tail + [self.C_mid, self.C_tail, (self.s1aT, None)] + self.D_tail}
-        for key, out in self.frag.items():
-            layer, bn, k0, K = src[key]
-            add(1, out, layer, bn, k0, K, *wts[key].shape)
+        for w in self.chain_w:
+            layer, bn, k0, K = src[id(w)]
+            add(1, self.frag[id(w)], layer, bn, k0, K, *w.shape)
         for w in self.wide:
             layer, bn, k0, K = src[id(w)]
             add(2, self.frag6[id(w)], layer, bn, k0, K, *w.shape)
-        fcs = (self.t1["f1"], self.t1["f2"], self.t2["f1"], self.t2["f2"], self.t2["f3"], self.s1g)
-        for w in fcs:
+        for w in self.fcs:
             layer, bn, k0, K = src[id(w)]
             add(1, self.fcf[id(w)], layer, bn, k0, K, _pad(w.shape[1], 16), w.shape[0])
+        if not self.seg:  # conv3 for ndnet_pn_cls_head_run: W^T fragment-major and the bias, classes padded to 16
+            add(1, self.h3f, m.conv3, None, 0, 256, 256, self.Cp)
+            bias(self.h3b, m.conv3, None)
         return jobs
 
     def can_refold(self, tensors) -> bool:
@@ -513,7 +574,8 @@ class _Workspace:
         f32 = dict(dtype=torch.float32, device=dev)
         Fp = W.C_tail[0].shape[1]
         # the three max-pooled vectors, -inf before the atomic maxima (ReLU'd maxima are >= 0)
-        # -inf before the first forward; chain D re-arms it for the next one
+        # -inf before the first forward; the last launch (chain D, or the classification head's
+        # ndnet_pn_cls_head_run) re-arms it for the next one
         self.gbuf = torch.full((B, 2048 + Fp), float("-inf"), **f32)
         self.g1, self.g2, self.g3 = self.gbuf[:, :1024], self.gbuf[:, 1024:2048], self.gbuf[:, 2048:]
         self.h1, self.h2 = torch.empty((B, 512), **f32), torch.empty((B, 256), **f32)
@@ -531,15 +593,15 @@ class _Workspace:
             (3, W.A, (1, 1, 1), 0, dict(gmax=self.g1)),
             (12, [(self.w1T, W.c1b)] + W.B_tail, (0, 1, 1, 1), 0, dict(gmax=self.g2)),
             (12, [(self.w1t2, self.b1t2), W.C_mid, W.C_tail], (0, 0, 0), 0, dict(gmax=self.g3)),
-            # the 512-wide seg conv1 output feeds conv2 chunk by chunk (never stored whole)
-            (12, [(self.w1t2, self.b1t2), (W.s1aT, self.cvec)] + W.D_tail, (0, 1, 1, 1, 0), 1,
-             dict(out_cols=W.C1, fuse=(1,))),
         ]
+        if W.seg:  # the 512-wide seg conv1 output feeds conv2 chunk by chunk (never stored whole)
+            self.specs.append((12, [(self.w1t2, self.b1t2), (W.s1aT, self.cvec)] + W.D_tail, (0, 1, 1, 1, 0), 1,
+                               dict(out_cols=W.C1, fuse=(1,))))
         self.N = N
         self.structs = {}
 
     def hip_layers(self, mode: str) -> list:
-        """The four chains' layers for ``_build_chain`` in one precision mode:
+        """The chains' layers (A-D; A-C for a classification model) for ``_build_chain`` in one precision mode:
         every layer with a split-bf16 copy takes the mode's prec (all modes
         read the same ``frag6``); "fp32" and the other layers read ``frag``."""
         W = self.W
@@ -554,13 +616,15 @@ class _Workspace:
         # chain C's layer 0: conv1 with t1 and t2 folded (ndnet_pn_fold_t2_run), or
         # with t1 only and t2 folded in its prologue (NDNET_PN_FOLD_T2=chain)
         LC = (self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64) if FOLD_T2_KERNEL else L1
-        return [
+        layers = [
             [shared(x) for x in W.A],
             [L1] + [shared(x) for x in W.B_tail],
             [LC, shared(W.C_mid), shared(W.C_tail)],
-            [(self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64), shared((W.s1aT, self.cvec))] +
-            [shared(x) for x in W.D_tail],
         ]
+        if W.seg:
+            layers.append([(self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64), shared((W.s1aT, self.cvec))] +
+                          [shared(x) for x in W.D_tail])
+        return layers
 
     def chain(self, i: int, x: torch.Tensor, chain_fn=None, out=None) -> None:
         in_cols, layers, relus, mode, kw = self.specs[i]
@@ -571,14 +635,15 @@ class _Workspace:
             chain_fn(x, self.N, in_cols, layers, relus, mode, **kw)
             return
         structs = self.structs.get(self.mode)
+        W = self.W
         if structs is None:
             structs = self.structs[self.mode] = [_build_chain(self.N, s[0], hl, s[2], s[3], **s[4])
                                                  for s, hl in zip(self.specs, self.hip_layers(self.mode))]
-            # the last chain re-arms the max-pool buffer (-inf) for the next forward
-            structs[3].clear = self.gbuf.data_ptr()
-            structs[3].clear_count = self.gbuf.numel()
+            if W.seg:  # the last chain re-arms the max-pool buffer (-inf) for the next forward
+                structs[3].clear = self.gbuf.data_ptr()
+                structs[3].clear_count = self.gbuf.numel()
             if HEAD3_IN_CHAIN:  # chain B computes t1 and its conv1 weights itself
-                W, cb = self.W, structs[1]
+                cb = structs[1]
                 cb.head_h2, cb.head_ld, cb.head_K = self.h2.data_ptr(), self.h2.stride(0), self.h2.shape[1]
                 cb.head_w3, cb.head_b3 = W.t1["f3"].data_ptr(), W.t1["c3"].data_ptr()
                 cb.head_basis, cb.head_kin, cb.head_nout = W.t1_basis.data_ptr(), 12, 64
@@ -694,7 +759,16 @@ def _glue_hip(W, ws, B: int):
     def seg_bias():
         fc(ws.g3[:, : W.F], W.s1g, W.s1b, ws.cvec, False)
 
-    return head_a, head_b, seg_bias
+    def cls_head(out):
+        # g3's columns past F are chain C's zero padding, matched by zero weight rows
+        fc(ws.g3[:, : W.F], W.h1w, W.h1b, ws.h1, True)
+        fc(ws.h1, W.h2w, W.h2b, ws.h2, True)
+        rc = _lib.lib().ndnet_pn_cls_head_run(ws.h2.data_ptr(), ws.h2.stride(0), W.h3f.data_ptr(), W.h3b.data_ptr(),
+                                              out.data_ptr(), out.stride(0), None, 0, B, ws.h2.shape[1], W.Cp, W.C,
+                                              ws.gbuf.data_ptr(), ws.gbuf.numel(), st())
+        _lib.check(rc, "ndnet_pn_cls_head_run")
+
+    return head_a, head_b, (seg_bias if W.seg else cls_head)
 
 
 def _glue_torch(W, ws, B: int):
@@ -711,7 +785,12 @@ def _glue_torch(W, ws, B: int):
     def seg_bias():
         torch.addmm(W.s1b, ws.g3[:, : W.F], W.s1bT, out=ws.cvec)
 
-    return head_a, head_b, seg_bias
+    def cls_head(out):
+        torch.addmm(W.h1b, ws.g3[:, : W.F], W.h1w[:, :, 0].t(), out=ws.h1).relu_()
+        torch.addmm(W.h2b, ws.h1, W.h2w[:, :, 0].t(), out=ws.h2).relu_()
+        out.copy_(torch.softmax(torch.addmm(W.h3b[: W.C], ws.h2, W.h3w[:, :, 0].t()), dim=1))
+
+    return head_a, head_b, (seg_bias if W.seg else cls_head)
 
 
 # Workspace slot of the forwards launched from now on (``workspace_slot``).
@@ -745,14 +824,11 @@ class workspace_slot:
         return False
 
 
-def segmentation_forward(model, points: torch.Tensor, covariances: torch.Tensor, chain=None) -> torch.Tensor:
-    """model(points [B,N,3], covariances [B,N,9]) -> log-probs [B,N,C+1], eval mode.
-
-    The split-bf16 layers run in the model's precision mode as of this call
-    (``model_precision``).  ``chain``: None runs every step on the HIP kernels; a chain emulator
-    (``_chain_torch``) runs the chains and the per-cloud steps as torch ops.
-    Concurrent forwards (different streams, no order) need different
-    ``workspace_slot``s."""
+def _features(model, points: torch.Tensor, covariances: torch.Tensor, chain):
+    """What both forwards share: the fold, the workspace of this shape and
+    slot, the [B,N,12] input block, and chains A, B and C with the per-cloud
+    steps between them.  Leaves the pooled global feature in ``ws.g3`` and
+    returns (W, ws, x, the glue's last step)."""
     mode = model_precision(model)
     cache = _folded(model)
     W = cache["W"]
@@ -769,7 +845,7 @@ def segmentation_forward(model, points: torch.Tensor, covariances: torch.Tensor,
         x = points.as_strided((B, N, 12), (N * 12, 12, 1))
     else:
         x = torch.cat((points, covariances), dim=2).float().contiguous()
-    head_a, head_b, seg_bias = (_glue_hip if chain is None else _glue_torch)(W, ws, B)
+    head_a, head_b, last = (_glue_hip if chain is None else _glue_torch)(W, ws, B)
     if chain is not None:
         ws.gbuf.fill_(float("-inf"))
     ws.chain(0, x, chain)   # A: TNet(3) -> g1
@@ -777,9 +853,40 @@ def segmentation_forward(model, points: torch.Tensor, covariances: torch.Tensor,
     ws.chain(1, x, chain)   # B: conv1 (+t1) then TNet(64) -> g2
     head_b()                # t2, t2 @ [W2^T | Ws1a^T]
     ws.chain(2, x, chain)   # C: conv2, conv3, max over points -> g3
+    return W, ws, x, last
+
+
+def segmentation_forward(model, points: torch.Tensor, covariances: torch.Tensor, chain=None) -> torch.Tensor:
+    """model(points [B,N,3], covariances [B,N,9]) -> log-probs [B,N,C+1], eval mode.
+
+    The split-bf16 layers run in the model's precision mode as of this call
+    (``model_precision``).  ``chain``: None runs every step on the HIP kernels; a chain emulator
+    (``_chain_torch``) runs the chains and the per-cloud steps as torch ops.
+    Concurrent forwards (different streams, no order) need different
+    ``workspace_slot``s."""
+    W, ws, x, seg_bias = _features(model, points, covariances, chain)
+    B, N, _ = points.shape
     seg_bias()              # the broadcast global feature as a per-cloud bias of the seg head
-    out = torch.empty((B, N, W.C1), dtype=torch.float32, device=dev)
+    out = torch.empty((B, N, W.C1), dtype=torch.float32, device=points.device)
     ws.chain(3, x, chain, out=out)
     if chain is not None:
         ws.gbuf.fill_(float("-inf"))  # the HIP path expects it armed (chain D re-arms it there)
     return out
+
+
+def classification_forward(model, points: torch.Tensor, covariances: torch.Tensor, chain=None) -> torch.Tensor:
+    """model(points [B,N,3], covariances [B,N,9]) -> class probabilities
+    [B, num_classes, 1] (the reference's shape, ndtnet.py:188-196), eval mode.
+
+    Chains A-C, the per-cloud steps, the workspace (same cache key and
+    ``workspace_slot``) and the precision modes are ``segmentation_forward``'s;
+    the head -- relu(conv1), relu(conv2) on ``ndnet_pn_fc_mfma_run``, then conv3
+    and the softmax in one ``ndnet_pn_cls_head_run``, which also re-arms the
+    max-pool buffer -- stays on the fp32 MFMA in every mode.  ``chain``: as for
+    ``segmentation_forward`` (the head then runs as torch ops too)."""
+    W, ws, x, cls_head = _features(model, points, covariances, chain)
+    out = torch.empty((points.shape[0], W.C), dtype=torch.float32, device=points.device)
+    cls_head(out)
+    if chain is not None:
+        ws.gbuf.fill_(float("-inf"))  # the HIP path expects it armed (the head kernel re-arms it there)
+    return out.unsqueeze(2)

@@ -113,7 +113,10 @@ class GraphedSegmentation:
     """Replays ``model(*ndt_preprocessing(num_nds, points)[:2])`` from a graph.
 
     Args:
-        model: an ``NDTNetSegmentation`` in eval mode on a cuda device.  Its
+        model: an ``NDTNetSegmentation`` -- or an ``NDTNetClassification``,
+            which keeps the same folded-weight cache (``model._hip``) and is
+            taken as it is; the output is then its ``[B, num_classes, 1]``
+            probabilities -- in eval mode on a cuda device.  Its
             weights are folded at capture time; the replays follow later
             in-place weight changes (re-folded before the replay, see
             ``_Pinned``); a replaced parameter tensor makes the replay raise.
@@ -220,6 +223,10 @@ class PipelinedSegmentation:
     ``levels`` (config C5): the NDT stage is ndt_multiscale (downsample to
     levels[0], prune to each further level) and the forward stage one forward
     per level; the output is then the list of per-level log-probs.
+
+    ``model`` may be an ``NDTNetClassification`` as well (the stages only call
+    ``model(points, covariances)`` and pin ``model._hip``): the outputs are
+    then its ``[B, num_classes, 1]`` probabilities.
 
     The forward graphs keep the precision mode they were captured with
     (``model.precision`` or ``pointnet_hip.PRECISION`` at construction), as
