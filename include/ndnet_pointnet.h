@@ -81,13 +81,18 @@ typedef struct ndnet_pn_chain {
   // optional prologue (head_h2 != NULL; chain B): the TNet(3) tail of ndnet_pn_head3_run computed by
   // every workgroup of a cloud before layer 0, which reads its result -- t1[b] = h2[b] @ W3^T + b3 (9
   // outputs, the identity folded into b3) and conv1 with t1 folded, written fragment-major (K padded to
-  // 16) to L[0].w + b * L[0].w_cloud_stride (every workgroup writes the same bits); t1 to head_t1[b]
-  const float* head_h2;   // [B][head_ld]
+  // 16) to L[0].w + b * L[0].w_cloud_stride (every workgroup writes the same bits); t1 to head_t1[b].
+  // With head_h2 set, NDNET_ERR_ARG unless: head_w3, head_b3, head_basis and head_t1 are non-NULL;
+  // head_K >= 1 and head_ld >= head_K; 1 <= head_kin <= 16; L[0].K == 16 (the fold writes one k-group);
+  // head_nout == L[0].N; L[0].w_cloud_stride >= 16 * head_nout (each cloud its own weights); and, with
+  // head_K == 256 (h2's row and W3's rows are read as one float4 per lane), head_h2 and head_w3
+  // 16-byte aligned and head_ld % 4 == 0
+  const float* head_h2;   // [B][head_ld], head_ld >= head_K
   int32_t head_ld, head_K;
   const float* head_w3;   // [9][head_K]
   const float* head_b3;   // [9]
   const float* head_basis;  // [9][head_kin * head_nout]
-  int32_t head_kin, head_nout;
+  int32_t head_kin, head_nout;  // 1 <= head_kin <= 16; head_nout == L[0].N
   float* head_t1;         // [B][9]
   // optional prologue (fold_t2 != NULL; chains C and D, layer 0 on the VALU): TNet(64)'s feature
   // transform applied through layer 0 -- x_t2 = t2[b]^T (W0 x + b0) (ndtnet.py:150-157: bmm of the
@@ -131,6 +136,11 @@ int ndnet_pn_debug_stamps_clear(void);  /* zeroes them (timing builds; else -20)
  *                        w1f[b] = t1[b] @ basis ([9][kin * nout] row-major) --
  *                        conv1 with t1 folded, written fragment-major with K
  *                        padded to 16 (16 * nout floats per cloud)
+ * NDNET_ERR_ARG (-20) before any launch: ndnet_pn_fc_run for a NULL pointer,
+ * batch outside 1..16, K < 1 or K % 4, N < 1, ld_in % 4, ld_in < K,
+ * ld_out < N, or `in` / W not 16-byte aligned; ndnet_pn_head3_run (h2
+ * [batch][ld_h], W3 [9][K]) for a NULL pointer, batch < 1, K < 1, ld_h < K,
+ * kin outside 1..16, nout < 1 or nout % 16.
  * Same return codes as ndnet_pn_chain_run; graph-capturable. */
 int ndnet_pn_fc_run(const float *in, int ld_in, const float *W, const float *bias, float *out, int ld_out,
                     int batch, int K, int N, int relu, void *stream);

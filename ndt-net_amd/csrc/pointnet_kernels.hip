@@ -1802,7 +1802,7 @@ int ndnet_pn_cls_head_run(const float* in, int ld_in, const float* Wf, const flo
 int ndnet_pn_fc_run(const float* in, int ld_in, const float* W, const float* bias, float* out, int ld_out, int batch,
                     int K, int N, int relu, void* stream) {
   if (!in || !W || !bias || !out || batch <= 0 || batch > 16 || K <= 0 || K % 4 || N <= 0 || ld_in % 4 ||
-      ((uintptr_t)in | (uintptr_t)W) % 16)
+      ld_in < K || ld_out < N || ((uintptr_t)in | (uintptr_t)W) % 16)
     return -20;
   hipStream_t st = (hipStream_t)stream;
   switch (K % 256 == 0 && K <= 1024 ? K / 256 : 0) {
@@ -1815,8 +1815,8 @@ int ndnet_pn_fc_run(const float* in, int ld_in, const float* W, const float* bia
 
 int ndnet_pn_head3_run(const float* h2, int ld_h, const float* W3, const float* b3, const float* basis, float* t1,
                        float* w1f, int batch, int K, int kin, int nout, void* stream) {
-  if (!h2 || !W3 || !b3 || !basis || !t1 || !w1f || batch <= 0 || K <= 0 || kin <= 0 || kin > 16 || nout <= 0 ||
-      nout % 16)
+  if (!h2 || !W3 || !b3 || !basis || !t1 || !w1f || batch <= 0 || K <= 0 || ld_h < K || kin <= 0 || kin > 16 ||
+      nout <= 0 || nout % 16)
     return -20;
   k_pn_head3<<<batch, 256, 0, (hipStream_t)stream>>>(h2, ld_h, W3, b3, basis, t1, w1f, K, kin, nout);
   return hipGetLastError() == hipSuccess ? 0 : -21;
@@ -1965,6 +1965,18 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
     const int inside = (r ? r0f : 0) + p_in;
     if (r == 1 || inside + fb <= r0f) fbuf_off = inside;
     total = fbuf_off + (size_t)fb > total ? fbuf_off + (size_t)fb : total;
+  }
+  if (args->head_h2) {  // the TNet(3) tail in the prologue: it writes layer 0's per-cloud weights (one k-group)
+    const ndnet_pn_layer& L0 = args->L[0];
+    if (!args->head_w3 || !args->head_b3 || !args->head_basis || !args->head_t1) PN_ARG_FAIL();
+    if (args->head_K < 1 || args->head_ld < args->head_K || args->head_kin < 1 || args->head_kin > 16) PN_ARG_FAIL();
+    // head_nout != L0.N would write the [16][64] LDS copy (VALU layer 0) out of its shape; a shorter
+    // stride would make the clouds overwrite each other's weights
+    if (L0.K != 16 || args->head_nout != L0.N || L0.w_cloud_stride < 16 * (int64_t)args->head_nout) PN_ARG_FAIL();
+    // head_K == 256 reads h2's row and W3's rows as one float4 per lane
+    if (args->head_K == 256 &&
+        (((uintptr_t)args->head_h2 | (uintptr_t)args->head_w3) % 16 || args->head_ld % 4))
+      PN_ARG_FAIL();
   }
   if ((args->fold_out_w || args->fold_out_b) && (!args->fold_t2 || !args->fold_out_w || !args->fold_out_b))
     PN_ARG_FAIL();

@@ -497,6 +497,26 @@ def test_head3_in_chain_equals_head3_kernel(monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("flag", ["FC_MFMA", "FOLD_T2_KERNEL"])
+def test_alternate_glue_paths_match_torch(monkeypatch, flag):
+    """The paths the defaults leave unused -- the FC layers on the GEMV kernels
+    (NDNET_PN_FC=gemv: ndnet_pn_fc_run) and t2 folded in chain C's prologue and
+    published for chain D (NDNET_PN_FOLD_T2=chain) -- on a fresh F = 64, C = 5
+    model; set before its first forward, since the argument blocks are cached
+    per model."""
+    from ndnet.models import pointnet_hip as ph
+    monkeypatch.setattr(ph, flag, False)
+    torch.manual_seed(13)
+    pts, cov = torch.randn(3, 77, 3).cuda(), torch.randn(3, 77, 9).cuda() * 0.1
+    m = _model(64, 5, "cuda")
+    with torch.no_grad():
+        out = m(pts, cov)
+        ref = m.forward_torch(pts, cov)
+    assert out.shape == (3, 77, 6)
+    assert (out - ref).abs().max().item() < TOL
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("B,N", [(16, 500), (4, 77), (2, 1000)])
 def test_chain_t32_equals_t64(monkeypatch, B, N):
     """The 32-point-tile chain build (ndnet_pn_chain_run_t32: 8 waves, two row

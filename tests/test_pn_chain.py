@@ -8,7 +8,9 @@ same float64 result,  e_hip <= 3 e_t + 1e-6 max |float64 result|  (the
 factor covers summation order only; a split-bf16 layer that lost a plane sits
 near 2^-16 relative).  Every case runs on both builds (64-point tiles, 16
 waves; 32-point tiles, 8 waves).  Inputs are on the scale of NDT rows: means
-within +-10, covariance entries of both signs spanning 1e-4 .. 60."""
+within +-10, covariance entries of both signs spanning 1e-4 .. 60.  The two
+optional prologues (head_*, fold_t2) are checked the same way, what they
+publish included, with torch's fp32 addmm / matmul of the fold as e_t."""
 import ctypes
 import math
 
@@ -72,7 +74,8 @@ class _Case:
         B, N, _ = x.shape
         self.B, self.N, self.n_last = B, N, layers[-1]["N"]
         self.ref = _ref64(x, in_cols, layers, mode, out_cols)
-        dev_layers = [(L["wT"].cuda(), L["b"].cuda()) for L in layers]
+        # "dev": the layer as torch computes it in fp32 on the device, where wT / b are its float64 reference
+        dev_layers = [L["dev"] if "dev" in L else (L["wT"].cuda(), L["b"].cuda()) for L in layers]
         # torch fp32 on the device
         if mode == 0:
             t = torch.full((B, self.n_last), float("-inf"), device="cuda")
@@ -303,6 +306,261 @@ def test_clear_rearms_exactly_its_range(count):
     c.check("clear")
 
 
+# ---- the two optional prologues (head_*: TNet(3)'s tail; fold_t2: TNet(64)'s transform through layer 0) ----
+
+def _sentinel(*shape):
+    t = torch.empty(*shape, dtype=torch.float32, device="cuda")
+    t.view(torch.int32).fill_(NAN_BITS)
+    return t
+
+
+def _kept(t):
+    return bool((t.contiguous().view(torch.int32) == NAN_BITS).all())
+
+
+def _padded(x, ld):
+    """[rows][ld] with x in the first columns and NaN in the pad."""
+    out = torch.full((x.shape[0], ld), float("nan"))
+    out[:, : x.shape[1]] = x
+    return out
+
+
+def _rows16(nout):
+    """The row k of every position of a fragment-major [16][nout] layer."""
+    return _ph()._frag(torch.arange(16.0)[:, None].expand(16, nout).contiguous())
+
+
+def _report(name, got, ref, e_t, bad):
+    """The bound of this file on one published tensor; prints e_hip, e_t and the ratio."""
+    e_hip = (got - ref).abs().max().item()
+    scale = ref.abs().max().item()
+    print(f"{name}: e_hip {e_hip:.3e} e_t {e_t:.3e} scale {scale:.3e} ratio {e_hip / max(e_t, 1e-300):.2f}")
+    if not (bool(torch.isfinite(got).all()) and e_hip <= 3 * e_t + 1e-6 * scale):
+        bad.append((name, e_hip, e_t, scale))
+
+
+def _run_checked(c, name, entry, bad):
+    """One launch of `entry`: the chain's output against float64 under the bound."""
+    got = c.run(entry)
+    _report(f"{name} {entry[9:]} out", got, c.ref, c.e_t, bad)
+
+
+class _Head:
+    """The head prologue's operands for B clouds: h2 (non-negative, rows of
+    head_K + 4 floats with NaN pads), W3, b3 and a dense basis [9][kin * nout]
+    (not the model's 0/1 structure: a wrong a, k or n index shows); t1 and
+    layer 0's per-cloud W^T [B][16][nout] (rows kin..15 zero) in float64 and
+    as torch computes them in fp32 on the device."""
+
+    def __init__(self, g, B, head_K, kin, nout):
+        self.B, self.K, self.kin, self.nout, self.ld = B, head_K, kin, nout, head_K + 4
+        h2 = torch.relu(torch.randn(B, head_K, generator=g) + 1.0)
+        w3, b3 = torch.randn(9, head_K, generator=g) / math.sqrt(head_K), torch.randn(9, generator=g) * 0.5
+        basis = torch.randn(9, kin * nout, generator=g) / 3.0
+        pad = (0, 0, 0, 16 - kin)
+        self.t1_ref = h2.double() @ w3.double().t() + b3.double()
+        self.w_ref = torch.nn.functional.pad((self.t1_ref @ basis.double()).view(B, kin, nout), pad)
+        assert (self.t1_ref[1:] - self.t1_ref[:-1]).abs().amax(dim=1).min() > 1e-3  # the clouds differ
+        self.h2, self.w3, self.b3, self.basis = _padded(h2, self.ld).cuda(), w3.cuda(), b3.cuda(), basis.cuda()
+        t1_t = torch.addmm(self.b3, h2.cuda(), self.w3.t())
+        self.w_t = torch.nn.functional.pad(torch.matmul(t1_t, self.basis).view(B, kin, nout), pad)
+        self.e_t1 = (t1_t.double().cpu() - self.t1_ref).abs().max().item()
+        self.e_w = (self.w_t.double().cpu() - self.w_ref).abs().max().item()
+
+    def layer0(self, g, relu=1):
+        L = _layer(g, 16, self.nout, F32, relu)
+        L.update(wT=self.w_ref, dev=(self.w_t, L["b"].cuda()))
+        return L
+
+    def attach(self, c):
+        """Points chain `c` at the prologue: layer 0's per-cloud weights are a
+        sentinel-filled buffer with 64 floats of pad per cloud."""
+        self.size = 16 * self.nout
+        self.wbuf, self.t1 = _sentinel(self.B, self.size + 64), _sentinel(self.B * 9 + 7)
+        ch = c.ch
+        ch.L[0].w, ch.L[0].w_cloud_stride = self.wbuf.data_ptr(), self.wbuf.stride(0)
+        ch.head_h2, ch.head_ld, ch.head_K = self.h2.data_ptr(), self.ld, self.K
+        ch.head_w3, ch.head_b3, ch.head_basis = self.w3.data_ptr(), self.b3.data_ptr(), self.basis.data_ptr()
+        ch.head_kin, ch.head_nout, ch.head_t1 = self.kin, self.nout, self.t1.data_ptr()
+
+    def check(self, c, name):
+        """Both builds: the output, head_t1 and the published layer 0 against float64."""
+        bad = []
+        rows = _rows16(self.nout)
+        for entry in BUILDS:
+            self.wbuf.view(torch.int32).fill_(NAN_BITS)
+            self.t1.view(torch.int32).fill_(NAN_BITS)
+            _run_checked(c, name, entry, bad)
+            assert _kept(self.t1[self.B * 9:]) and _kept(self.wbuf[:, self.size:]), f"{entry}: pads were written"
+            _report(f"{name} {entry[9:]} t1", self.t1[: self.B * 9].view(self.B, 9).double().cpu(), self.t1_ref,
+                    self.e_t1, bad)
+            w = self.wbuf[:, : self.size].cpu()
+            _report(f"{name} {entry[9:]} L[0].w", w.double(), _ph()._frag(self.w_ref), self.e_w, bad)
+            assert bool((w[:, rows >= self.kin] == 0).all()), f"{entry}: rows kin..15 are not exactly 0"
+        assert not bad, bad
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [1, 33, 130])
+@pytest.mark.parametrize("kin", [12, 3])
+@pytest.mark.parametrize("head_K", [256, 64, 100])
+def test_head_prologue_valu_layer0(head_K, kin, N):
+    """head_* with layer 0 on the VALU (16 -> 64, 64 -> 128 x6, 128 -> 64,
+    pooled): head_K 256 is the one-float4-per-lane path, 64 and 100 the strided
+    loop; kin = in_cols = 12 and 3.  The whole thing in float64: t1, W0[b], the
+    chain.  Only the cloud's first workgroup publishes L[0].w[b]."""
+    g = _gen(900 + head_K + kin + N)
+    hd = _Head(g, 3, head_K, kin, 64)
+    layers = [hd.layer0(g), _layer(g, 64, 128, X6, 1), _layer(g, 128, 64, F32, 0)]
+    c = _Case(_nd_rows(3, N, g), kin, layers, 0)
+    hd.attach(c)
+    hd.check(c, f"head valu K={head_K} kin={kin} N={N}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [1, 33, 130])
+@pytest.mark.parametrize("case", ["single", "nout128", "kin16"])
+def test_head_prologue_mfma_layer0(case, N):
+    """head_* with layer 0 on the MFMA path, where every workgroup stores layer
+    0's weights to memory and its layer 0 loads them back after a workgroup
+    barrier: a one-layer chain 16 -> 64; 16 -> 128 (head_nout = 128), 128 ->
+    64; and in_cols = x_ld = kin = 16 (16 -> 64, 64 -> 64).  All pooled."""
+    g = _gen(950 + N + {"single": 0, "nout128": 1000, "kin16": 2000}[case])
+    if case == "single":
+        hd = _Head(g, 3, 256, 12, 64)
+        layers, x, in_cols = [hd.layer0(g)], _nd_rows(3, N, g), 12
+    elif case == "nout128":
+        hd = _Head(g, 3, 100, 12, 128)
+        layers, x, in_cols = [hd.layer0(g), _layer(g, 128, 64, F32, 0)], _nd_rows(3, N, g), 12
+    else:
+        hd = _Head(g, 3, 64, 16, 64)
+        layers, x, in_cols = [hd.layer0(g), _layer(g, 64, 64, F32, 0)], _nd_rows(3, N, g, x_ld=16), 16
+    c = _Case(x, in_cols, layers, 0)
+    assert c.ch.x_ld == x.shape[2]
+    hd.attach(c)
+    hd.check(c, f"head mfma {case} N={N}")
+
+
+class _Fold:
+    """The fold_t2 prologue's operands for 3 clouds: a per-cloud layer 0 (W0^T
+    [12][64] in a K = 16 fragment, bias b0) and a dense t2 per cloud in rows
+    of fold_ld floats (NaN pads); chain 16 -> 64, 64 -> 128 (prec1), 128 ->
+    64, pooled.  float64: layer 0 is W0'[b] = W0^T[b] t2[b], b0'[b] = b0^T
+    t2[b], its relu flag applied after."""
+
+    def __init__(self, seed, N, relu0, prec1, fold_ld, prefill=None):
+        ph = _ph()
+        g = _gen(seed)
+        B = self.B = 3
+        w0 = torch.randn(B, 12, 64, generator=g) / math.sqrt(12)
+        b0, t2 = torch.randn(64, generator=g) * 0.5, torch.randn(B, 64, 64, generator=g) / 8.0
+        pad = (0, 0, 0, 4)
+        self.w_ref = torch.nn.functional.pad(w0.double() @ t2.double(), pad)
+        self.b_ref = b0.double() @ t2.double()                                   # [B][64]
+        assert (self.b_ref[1:] - self.b_ref[:-1]).abs().amax(dim=1).min() > 1e-3  # the clouds differ
+        self.w0f = ph._frag(torch.nn.functional.pad(w0, pad)).cuda()             # [B][1024]
+        self.b0, t2d = b0.cuda(), t2.cuda()
+        self.t2, self.fold_ld = _padded(t2.view(B, 4096), fold_ld).cuda(), fold_ld
+        w_t = torch.nn.functional.pad(torch.matmul(w0.cuda(), t2d), pad)
+        b_t = torch.matmul(self.b0, t2d)
+        self.e_w = (w_t.double().cpu() - self.w_ref).abs().max().item()
+        self.e_b = (b_t.double().cpu() - self.b_ref).abs().max().item()
+        l0 = dict(wT=self.w_ref, b=self.b_ref, K=16, N=64, prec=F32, relu=relu0, fuse=False, dev=(w_t, b_t))
+        self.layers = [l0, _layer(g, 64, 128, prec1, 1), _layer(g, 128, 64, F32, 0)]
+        self.x = _nd_rows(B, N, g)
+        c = self.c = _Case(self.x, 12, self.layers, 0)
+        # the HIP chain: the untransformed layer 0 and t2
+        L0 = c.ch.L[0]
+        L0.w, L0.w_cloud_stride, L0.bias, L0.bias_cloud_stride = self.w0f.data_ptr(), 1024, self.b0.data_ptr(), 0
+        c.ch.fold_t2, c.ch.fold_ld = self.t2.data_ptr(), fold_ld
+        self.prefill = prefill
+        self.out_w, self.out_b = torch.empty(B, 1024, device="cuda"), torch.empty(B * 64 + 8, device="cuda")
+        if prefill is not None:
+            c.ch.fold_out_w, c.ch.fold_out_b = self.out_w.data_ptr(), self.out_b.data_ptr()
+
+    def run(self, name, entry, bad):
+        """One launch: the output and, when published, fold_out_w / fold_out_b
+        against float64; rows 12..15 of fold_out_w keep their pre-fill."""
+        self.out_w.view(torch.int32).fill_(self.prefill or 0)
+        self.out_b.view(torch.int32).fill_(NAN_BITS)
+        _run_checked(self.c, name, entry, bad)
+        if self.prefill is None:
+            return
+        rows = _rows16(64)
+        w = self.out_w.cpu()
+        assert bool((w[:, rows >= 12].contiguous().view(torch.int32) == self.prefill).all()), "rows 12..15 were written"
+        assert _kept(self.out_b[self.B * 64:])
+        _report(f"{name} {entry[9:]} fold_out_w", w[:, rows < 12].double(), _ph()._frag(self.w_ref)[:, rows < 12],
+                self.e_w, bad)
+        _report(f"{name} {entry[9:]} fold_out_b", self.out_b[: self.B * 64].view(self.B, 64).double().cpu(), self.b_ref,
+                self.e_b, bad)
+
+    def kernel(self):
+        """ndnet_pn_fold_t2_run on the same operands: (outf, outb) on the CPU."""
+        from ndnet import _lib
+        outf, outb = torch.zeros(self.B, 1024, device="cuda"), torch.zeros(self.B, 64, device="cuda")
+        rc = _lib.lib().ndnet_pn_fold_t2_run(self.w0f.data_ptr(), 1024, self.b0.data_ptr(), self.t2.data_ptr(),
+                                             self.fold_ld, outf.data_ptr(), outb.data_ptr(), self.B,
+                                             _lib.stream_ptr(outf.device))
+        assert rc == 0
+        torch.cuda.synchronize()
+        return outf.cpu(), outb.cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [1, 33, 130])
+@pytest.mark.parametrize("fold_ld", [4096, 4160])
+@pytest.mark.parametrize("prec1", [F32, X6], ids=["fp32", "x6"])
+@pytest.mark.parametrize("relu0", [0, 1])
+def test_fold_t2_prologue(relu0, prec1, fold_ld, N):
+    """fold_t2 with fold_out_w / fold_out_b: x_t2 = t2[b]^T (W0 x + b0) carried
+    through the chain, layer 0 without a ReLU (the model's case) and with one,
+    layer 1 reading fp32 rows or the bf16 planes layer 0 writes.  The published
+    tensors against float64 and, within the same bound (not bit-equal: FMAs in
+    one, the MFMA in the other), against ndnet_pn_fold_t2_run's."""
+    f = _Fold(1100 + 8 * N + 4 * relu0 + 2 * prec1 + fold_ld, N, relu0, prec1, fold_ld, prefill=NAN_BITS)
+    kf, kb = f.kernel()
+    rows = _rows16(64) < 12
+    name, bad = f"fold relu0={relu0} prec1={prec1} ld={fold_ld} N={N}", []
+    for entry in BUILDS:
+        f.run(name, entry, bad)
+        d_w = (f.out_w.cpu()[:, rows] - kf[:, rows]).abs().max().item()
+        d_b = (f.out_b[: 3 * 64].view(3, 64).cpu() - kb).abs().max().item()
+        print(f"{name} {entry[9:]}: |published - fold_t2_run| W {d_w:.3e} (e_t {f.e_w:.3e}) b {d_b:.3e} (e_t {f.e_b:.3e})")
+        if not d_w <= 3 * f.e_w + 1e-6 * f.w_ref.abs().max().item():
+            bad.append((name, entry, "W against the kernel", d_w, f.e_w))
+        if not d_b <= 3 * f.e_b + 1e-6 * f.b_ref.abs().max().item():
+            bad.append((name, entry, "b against the kernel", d_b, f.e_b))
+    assert not bad, bad
+
+
+@pytest.mark.gpu
+def test_fold_t2_prologue_without_publication():
+    """fold_out_w and fold_out_b NULL: the chain folds t2 for itself only."""
+    f = _Fold(1200, 130, 0, X6, 4096)
+    bad = []
+    for entry in BUILDS:
+        f.run("fold unpublished", entry, bad)
+    assert not bad, bad
+
+
+@pytest.mark.gpu
+def test_fold_t2_publication_feeds_a_second_chain():
+    """As chain D after chain C: a second chain runs the published W0'[b] and
+    b0'[b] as a plain per-cloud layer 0 (rows 12..15 zero-initialised, and
+    still zero after) and matches float64; once per build of the publisher."""
+    f = _Fold(1300, 130, 0, X6, 4096, prefill=0)
+    d = _Case(f.x, 12, f.layers, 0)
+    L0 = d.ch.L[0]
+    L0.w, L0.w_cloud_stride, L0.bias, L0.bias_cloud_stride = f.out_w.data_ptr(), 1024, f.out_b.data_ptr(), 64
+    assert not d.ch.fold_t2
+    bad = []
+    for entry in BUILDS:
+        f.run("fold publisher", entry, bad)
+        d.check(f"consumer of {entry[9:]}")
+    assert not bad, bad
+
+
 # ---- argument checks: rejected before any HIP call, so these run without a GPU ----
 
 def _arg_block(edit, device="cpu"):
@@ -375,4 +633,69 @@ def test_unedited_argument_block_is_accepted():
 def test_inconsistent_argument_blocks_are_rejected(case, capfd):
     """NDNET_ERR_ARG (-20) from both entry points, before anything is launched."""
     assert _arg_block(ARG_CASES[case]) == [-20, -20]
+    assert capfd.readouterr().err.count("invalid argument") == 2
+
+
+def _head_block(edit, device="cpu"):
+    """A valid chain with the head prologue (16 -> 64 per cloud, 64 -> 128, pooled; head_K = 256, kin 12),
+    changed by `edit(ch, tensors)`; returns what both entry points answer.  Over host memory by default."""
+    from ndnet import _lib
+    ph = _ph()
+    shapes = dict(w0=(2, 1024), b0=(64,), w1=(64 * 128,), b1=(128,), x=(2, 5, 12), gmax=(2, 128), h2=(2, 256),
+                  w3=(9, 256), b3=(9,), basis=(9, 12 * 64), t1=(2, 9))
+    t = {k: torch.zeros(*s, device=device) for k, s in shapes.items()}
+    ch = ph._build_chain(5, 12, [(t["w0"], 1024, t["b0"], 16, 64), (t["w1"], 0, t["b1"], 64, 128)], [1, 1], 0,
+                         gmax=t["gmax"])
+    ch.x = t["x"].data_ptr()
+    ch.head_h2, ch.head_ld, ch.head_K = t["h2"].data_ptr(), 256, 256
+    ch.head_w3, ch.head_b3, ch.head_basis = t["w3"].data_ptr(), t["b3"].data_ptr(), t["basis"].data_ptr()
+    ch.head_kin, ch.head_nout, ch.head_t1 = 12, 64, t["t1"].data_ptr()
+    edit(ch, t)
+    rcs = [getattr(_lib.lib(), e)(ctypes.byref(ch), 2, None) for e in BUILDS]
+    if device != "cpu":
+        torch.cuda.synchronize()
+    return rcs
+
+
+def _set(name, value):
+    return lambda ch, t: setattr(ch, name, value)
+
+
+def _layer0_k32(ch, t):  # a valid two-k-group layer 0 otherwise: region 0 widened for its input
+    ch.L[0].K, ch.max_width = 32, 32
+
+
+def _layer0_n128(ch, t):  # a 128-wide layer 0 (and layer 1 reading it) with head_nout left at 64
+    ch.L[0].N, ch.L[1].K, ch.max_width2 = 128, 128, 128
+
+
+HEAD_ARG_CASES = {
+    "NULL head_w3": _set("head_w3", None),
+    "NULL head_b3": _set("head_b3", None),
+    "NULL head_basis": _set("head_basis", None),
+    "NULL head_t1": _set("head_t1", None),
+    "head_K < 1": _set("head_K", 0),
+    "head_ld < head_K": lambda ch, t: (setattr(ch, "head_K", 100), setattr(ch, "head_ld", 96)),
+    "head_kin < 1": _set("head_kin", 0),
+    "head_kin > 16": _set("head_kin", 17),
+    "L[0].K != 16": _layer0_k32,
+    "head_nout != L[0].N": _set("head_nout", 128),
+    "L[0].N != head_nout": _layer0_n128,
+    "w_cloud_stride < 16 head_nout": lambda ch, t: setattr(ch.L[0], "w_cloud_stride", 512),
+    "shared layer 0": lambda ch, t: setattr(ch.L[0], "w_cloud_stride", 0),
+    "head_K 256, head_h2 misaligned": lambda ch, t: (setattr(ch, "head_h2", t["h2"].data_ptr() + 4), setattr(ch, "head_ld", 260)),
+    "head_K 256, head_w3 misaligned": lambda ch, t: setattr(ch, "head_w3", t["w3"].data_ptr() + 8),
+    "head_K 256, head_ld % 4": _set("head_ld", 258),
+}
+
+
+@pytest.mark.gpu
+def test_unedited_head_block_is_accepted():
+    assert _head_block(lambda ch, t: None, device="cuda") == [0, 0]
+
+
+@pytest.mark.parametrize("case", sorted(HEAD_ARG_CASES))
+def test_inconsistent_head_blocks_are_rejected(case, capfd):
+    """NDNET_ERR_ARG (-20) from both entry points, before anything is launched."""
+    assert _head_block(HEAD_ARG_CASES[case]) == [-20, -20]
     assert capfd.readouterr().err.count("invalid argument") == 2
