@@ -237,6 +237,31 @@ int ndnet_ndt_prune(void *plan, void *stream, uint64_t num_desired, float *d_out
                     double *d_out_points, double *d_out_covariances, uint16_t *d_out_classes16,
                     ndnet_ndt_stats *d_stats);
 
+/* The output row every input point was folded into (per-point segmentation
+ * labels: ndnet_segment.h maps the rows to classes).  Point i of cloud b
+ * contributed to an ND iff the cloud's rc is 0, i < 8 * (n / 8) (the
+ * reference's eight workers never read the tail, normal_distributions.c:34-35),
+ * its voxel key at the accepted grid is in grid and i lies below its worker's
+ * cut-off (a worker abandons its chunk at an out-of-grid point, :47-52).  Its
+ * row is the number of surviving NDs in lower voxels, where the ND survived
+ * the level last run and that number is < min(num_out, num_desired).  Every
+ * other point gets -1 (FILL_NONE) or the row whose fp32 mean -- columns 0..2
+ * of d_rows_block -- is nearest: squared distance in fp32 as dx * dx, + dy * dy,
+ * + dz * dz of fp32 differences, the lowest row on an exact tie (FILL_NEAREST).
+ * A point with a non-finite coordinate and every point of a cloud without rows
+ * (rc != 0) get -1 under both fills.
+ * Stream-ordered after the plan's last ndnet_ndt_run / ndnet_ndt_prune on the same d_points;
+ * no allocation, no synchronisation (capturable); reads the plan's state only.
+ * d_rows_block: the [B][num_desired][12] block that
+ * level wrote (may be NULL with FILL_NONE).  d_point_rows: [B][n] int32.
+ * NDNET_ERR_ARG: a NULL plan, points or output, num_desired 0 or above the
+ * plan's, an unknown fill, FILL_NEAREST without a block, or a plan whose last
+ * run was ndnet_ndt_run_f64 (float32 input only). */
+#define NDNET_POINT_FILL_NONE 0
+#define NDNET_POINT_FILL_NEAREST 1
+int ndnet_ndt_point_rows(void *plan, void *stream, const float *d_points, const float *d_rows_block,
+                         uint64_t num_desired, int fill, int32_t *d_point_rows);
+
 /* Stage timing with HIP events on the run's stream (bench.py): after
  * ndnet_ndt_set_timing(plan, 1), each run records events around its stages;
  * ndnet_ndt_stage_ms fills ms[6] of the last run (synchronises): path 1 =

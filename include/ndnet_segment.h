@@ -1,0 +1,45 @@
+/*
+ * ndnet_segment.h -- per-point segmentation labels on gfx950 (libndnet_amd.so).
+ *
+ * NDTNetSegmentation scores NDs ([B][k][C + 1] log-probs, one row per ND);
+ * ndnet_ndt_point_rows (ndnet_amd.h) gives the row every input point was
+ * folded into.  These plan-free entry points turn the two into a class per
+ * point and count a point-level confusion matrix.  Device pointers, stream
+ * ordered, no allocation and no synchronisation (capturable).  Return codes
+ * as ndnet_amd.h: NDNET_OK, NDNET_ERR_ARG (checked before any launch),
+ * NDNET_ERR_HIP.
+ */
+#ifndef NDNET_SEGMENT_H_
+#define NDNET_SEGMENT_H_
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* d_nd_labels[b][r] = first argmax of d_scores[b][r][0..cols) (NaN counts as a maximum, as
+ * ndnet_row_argmax / torch.argmax); d_point_labels[b][i] = d_nd_labels[b][row] or `unassigned`
+ * where d_point_rows[b][i] < 0 (or >= k).  d_nd_labels is caller scratch and an output.
+ * d_scores [B][k][cols] float32, d_point_rows and d_point_labels [B][n] int32, d_nd_labels [B][k] int32.
+ * NDNET_ERR_ARG for a NULL pointer or B, n, k or cols < 1. */
+int ndnet_seg_point_labels(const float *d_scores, const int32_t *d_point_rows, int B, uint64_t n, uint64_t k,
+                           int cols, int32_t unassigned, int32_t *d_nd_labels, int32_t *d_point_labels, void *stream);
+
+/* Confusion matrices up to this many classes are counted in a per-workgroup
+ * LDS histogram (cols * cols + 1 counters of 32 bits: 15.5 KB at 63) flushed
+ * with one 64-bit global atomic per non-zero counter; wider ones take a 64-bit
+ * global atomic per point. */
+#define NDNET_SEG_CONF_LDS_MAX_COLS 63
+
+/* d_conf[gt * cols + pred] += 1 over `count` points with 0 <= pred, gt < cols; every other point
+ * adds 1 to d_conf[cols * cols].  uint64 counters, the caller zeroes them.
+ * NDNET_ERR_ARG for a NULL pointer, count == 0 or cols < 1. */
+int ndnet_seg_confusion(const int32_t *d_pred, const int32_t *d_gt, uint64_t count, int cols,
+                        unsigned long long *d_conf, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* NDNET_SEGMENT_H_ */

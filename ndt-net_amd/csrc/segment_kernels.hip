@@ -1,0 +1,155 @@
+// segment_kernels.hip -- per-point segmentation labels on gfx950
+// (include/ndnet_segment.h): the class of every ND row, gathered to the points
+// through the rows ndnet_ndt_point_rows wrote, and the point-level confusion
+// matrix.
+//
+//   k_seg_nd_argmax     a wave per ND row: lanes stride the row's columns
+//                       (coalesced), the wave reduces to the first maximum
+//   k_seg_point_labels  a thread per point: one coalesced int32 load and store,
+//                       the ND labels (4 k bytes per cloud) from cache
+//   k_seg_confusion     grid-stride over the points; a per-workgroup LDS
+//                       histogram flushed with 64-bit global atomics, or one
+//                       64-bit global atomic per point for wide matrices
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/ndnet_amd.h"
+#include "../../include/ndnet_segment.h"
+
+namespace {
+
+#define SEG_HIPCHK(x)                                                         \
+  do {                                                                        \
+    hipError_t e_ = (x);                                                      \
+    if (e_ != hipSuccess) {                                                   \
+      fprintf(stderr, "ndnet_amd: %s: %s\n", #x, hipGetErrorString(e_));      \
+      return NDNET_ERR_HIP;                                                   \
+    }                                                                         \
+  } while (0)
+
+constexpr int kSegThreads = 256;
+
+// (v, i) beats (w, j) as the row's argmax: a NaN beats every number, a larger
+// number a smaller one, the lower index an equal value (torch.argmax)
+__device__ __forceinline__ bool seg_beats(float v, int i, float w, int j) {
+  const bool vn = v != v, wn = w != w;
+  if (vn || wn) return vn && (!wn || i < j);
+  return v > w || (v == w && i < j);
+}
+
+__global__ void __launch_bounds__(kSegThreads) k_seg_nd_argmax(const float* __restrict__ scores, uint64_t rows,
+                                                             int cols, int32_t* __restrict__ nd_labels) {
+  const uint64_t r = (uint64_t)blockIdx.x * (kSegThreads / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;  // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  const float* row = scores + r * (uint64_t)cols;
+  float bv = -__builtin_inff();
+  int bi = 0x7fffffff;  // a lane without a column loses to every column
+  for (int j = lane; j < cols; j += 64) {
+    const float v = row[j];
+    if (seg_beats(v, j, bv, bi)) {
+      bv = v;
+      bi = j;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (seg_beats(ov, oi, bv, bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+  if (lane == 0) nd_labels[r] = bi;
+}
+
+__global__ void __launch_bounds__(kSegThreads) k_seg_point_labels(const int32_t* __restrict__ point_rows,
+                                                                const int32_t* __restrict__ nd_labels, uint64_t n,
+                                                                uint64_t k, int32_t unassigned,
+                                                                int32_t* __restrict__ point_labels) {
+  const uint64_t i = (uint64_t)blockIdx.x * kSegThreads + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t b = blockIdx.y;
+  const int32_t row = point_rows[b * n + i];
+  point_labels[b * n + i] = row >= 0 && (uint64_t)row < k ? nd_labels[b * k + (uint64_t)row] : unassigned;
+}
+
+constexpr int kConfPPT = 8;        // points per thread per grid-stride round
+constexpr int kConfMaxBlocks = 1024;
+constexpr int kConfLdsCols = NDNET_SEG_CONF_LDS_MAX_COLS;
+constexpr int kConfLdsBins = kConfLdsCols * kConfLdsCols + 1;
+
+template <bool kLds>
+__global__ void __launch_bounds__(kSegThreads) k_seg_confusion(const int32_t* __restrict__ pred,
+                                                             const int32_t* __restrict__ gt, uint64_t count, int cols,
+                                                             unsigned long long* __restrict__ conf) {
+  __shared__ uint32_t hist[kLds ? kConfLdsBins : 1];
+  const uint32_t bins = (uint32_t)cols * (uint32_t)cols + 1u;
+  if constexpr (kLds) {
+    for (uint32_t j = threadIdx.x; j < bins; j += kSegThreads) hist[j] = 0;
+    __syncthreads();
+  }
+  // (32-bit LDS counters: a workgroup's share of the points, count / gridDim.x, stays far below 2^32)
+  const uint64_t stride = (uint64_t)gridDim.x * kSegThreads * kConfPPT;
+  for (uint64_t base = (uint64_t)blockIdx.x * kSegThreads * kConfPPT; base < count; base += stride) {
+    int32_t p[kConfPPT], g[kConfPPT];
+#pragma unroll
+    for (int q = 0; q < kConfPPT; q++) {
+      const uint64_t i = base + threadIdx.x + (uint64_t)kSegThreads * q;
+      p[q] = i < count ? pred[i] : 0;
+      g[q] = i < count ? gt[i] : 0;
+    }
+#pragma unroll
+    for (int q = 0; q < kConfPPT; q++) {
+      const uint64_t i = base + threadIdx.x + (uint64_t)kSegThreads * q;
+      if (i >= count) continue;
+      const bool in = p[q] >= 0 && p[q] < cols && g[q] >= 0 && g[q] < cols;
+      const uint32_t bin = in ? (uint32_t)g[q] * (uint32_t)cols + (uint32_t)p[q] : bins - 1u;
+      if constexpr (kLds) atomicAdd(&hist[bin], 1u);
+      else atomicAdd(&conf[bin], 1ull);
+    }
+  }
+  if constexpr (kLds) {
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < bins; j += kSegThreads) {
+      const uint32_t c = hist[j];
+      if (c) atomicAdd(&conf[j], (unsigned long long)c);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ndnet_seg_point_labels(const float* d_scores, const int32_t* d_point_rows, int B, uint64_t n, uint64_t k, int cols,
+                           int32_t unassigned, int32_t* d_nd_labels, int32_t* d_point_labels, void* stream) {
+  if (!d_scores || !d_point_rows || !d_nd_labels || !d_point_labels || B < 1 || n < 1 || k < 1 || cols < 1)
+    return NDNET_ERR_ARG;
+  const uint64_t rows = (uint64_t)B * k, pblocks = (n + kSegThreads - 1) / kSegThreads;
+  const uint64_t rblocks = (rows + kSegThreads / 64 - 1) / (kSegThreads / 64);
+  if (rblocks > 0x7fffffffull || pblocks > 0x7fffffffull || B > 65535) return NDNET_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  k_seg_nd_argmax<<<(uint32_t)rblocks, kSegThreads, 0, st>>>(d_scores, rows, cols, d_nd_labels);
+  k_seg_point_labels<<<dim3((uint32_t)pblocks, (uint32_t)B), kSegThreads, 0, st>>>(d_point_rows, d_nd_labels, n, k,
+                                                                                  unassigned, d_point_labels);
+  SEG_HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_seg_confusion(const int32_t* d_pred, const int32_t* d_gt, uint64_t count, int cols,
+                        unsigned long long* d_conf, void* stream) {
+  if (!d_pred || !d_gt || !d_conf || count == 0 || cols < 1 || cols > 46340) return NDNET_ERR_ARG;  // cols^2 + 1 in 32 bits
+  const uint64_t per = (uint64_t)kSegThreads * kConfPPT;
+  uint64_t blocks = (count + per - 1) / per;
+  if (blocks > (uint64_t)kConfMaxBlocks) blocks = kConfMaxBlocks;
+  hipStream_t st = (hipStream_t)stream;
+  if (cols <= kConfLdsCols) k_seg_confusion<true><<<(uint32_t)blocks, kSegThreads, 0, st>>>(d_pred, d_gt, count, cols, d_conf);
+  else k_seg_confusion<false><<<(uint32_t)blocks, kSegThreads, 0, st>>>(d_pred, d_gt, count, cols, d_conf);
+  SEG_HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+}  // extern "C"

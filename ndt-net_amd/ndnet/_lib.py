@@ -19,6 +19,8 @@ NDNET_OK = 0
 NDNET_ERR_ARG = -20
 NDNET_ERR_HIP = -21
 NDNET_ERR_SYNC = -22
+POINT_FILL = {"none": 0, "nearest": 1}  # NDNET_POINT_FILL_* (include/ndnet_amd.h)
+SEG_CONF_LDS_MAX_COLS = 63  # NDNET_SEG_CONF_LDS_MAX_COLS (include/ndnet_segment.h)
 
 
 class NdtStats(ctypes.Structure):
@@ -82,6 +84,10 @@ EXPORTS = {
     "ndnet_ndt_run": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_run_f64": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_prune": (_I, [_P, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "ndnet_ndt_point_rows": (_I, [_P, _P, _P, _P, _U64, _I, _P]),
+    # include/ndnet_segment.h
+    "ndnet_seg_point_labels": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_int32, _P, _P, _P]),
+    "ndnet_seg_confusion": (_I, [_P, _P, _U64, _I, _P, _P]),
     "ndnet_ndt_debug_dump": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_debug_set_epoch": (_I, [_P, ctypes.c_uint32]),
     "ndnet_ndt_debug_set_kl_fuse": (_I, [_P, _I]),

@@ -23,7 +23,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, segment
 from .preprocessing.ndtnet_preprocessing import NdtPlan, ndt_multiscale, ndt_preprocessing, get_plan
 
 
@@ -129,6 +129,14 @@ class GraphedSegmentation:
             levels[0], prune to each further level) and a forward per level;
             the output is the list of per-level log-probs.
 
+        point_labels: ``None`` (default: the graph as ever), ``"none"`` or
+            ``"nearest"``: the captured step also launches the points' rows
+            (``NdtPlan.point_rows`` with that fill) and their classes
+            (``ndnet.segment.point_labels``).  ``self.point_rows`` and
+            ``self.point_labels`` are then the static ``[B, N]`` int32 buffers,
+            overwritten by each replay.  For an ``NDTNetSegmentation`` without
+            ``levels`` only (``ValueError`` otherwise).
+
     ``points`` is the static float32 input buffer; ``__call__(new_points)``
     copies into it, replays, and returns the static ``[B, num_nds, C+1]``
     output buffer (overwritten by the next replay -- clone to keep it).
@@ -141,7 +149,16 @@ class GraphedSegmentation:
     """
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,
-                 device: Optional[torch.device] = None, warmup: int = 2, levels=None) -> None:
+                 device: Optional[torch.device] = None, warmup: int = 2, levels=None,
+                 point_labels: Optional[str] = None) -> None:
+        if point_labels is not None:  # (checked before any GPU work)
+            from .models.ndtnet import NDTNetSegmentation
+            if point_labels not in _lib.POINT_FILL:
+                raise ValueError(f"point_labels must be None, 'none' or 'nearest', got {point_labels!r}")
+            if not isinstance(model, NDTNetSegmentation):
+                raise ValueError("point_labels needs an NDTNetSegmentation (a classifier has no per-ND classes)")
+            if levels:
+                raise ValueError("point_labels is not available with levels")
         _lib.require_gpu()
         if model.training:
             raise ValueError("GraphedSegmentation needs an eval-mode model")
@@ -153,6 +170,12 @@ class GraphedSegmentation:
             num_nds = self.levels[0]
         self.model, self.num_nds, self.device = model, int(num_nds), dev
         self.points = torch.zeros((batch, num_points, 3), dtype=torch.float32, device=dev)
+        self.fill = point_labels
+        self.point_rows = self.point_labels = self._nd_labels = None
+        if point_labels is not None:
+            self.point_rows = torch.full((batch, num_points), -1, dtype=torch.int32, device=dev)
+            self.point_labels = torch.full((batch, num_points), -1, dtype=torch.int32, device=dev)
+            self._nd_labels = torch.zeros((batch, self.num_nds), dtype=torch.int32, device=dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.no_grad(), torch.cuda.stream(side):
@@ -170,7 +193,12 @@ class GraphedSegmentation:
         if self.levels:
             return [self.model(p, c) for p, c, _ in ndt_multiscale(self.levels, self.points)]
         p, c, _ = ndt_preprocessing(self.num_nds, self.points)
-        return self.model(p, c)
+        out = self.model(p, c)
+        if self.fill is not None:
+            rows = segment.point_rows(self.points, self.fill, ndt_preprocessing.last_plan,
+                                      ndt_preprocessing.last_rows, out=self.point_rows)
+            segment.point_labels(out, rows, out=self.point_labels, nd_labels=self._nd_labels)
+        return out
 
     def replay(self) -> torch.Tensor:
         self._pinned.check()
@@ -231,6 +259,12 @@ class PipelinedSegmentation:
     The forward graphs keep the precision mode they were captured with
     (``model.precision`` or ``pointnet_hip.PRECISION`` at construction), as
     ``GraphedSegmentation`` does.
+
+    Per-point labels (``GraphedSegmentation(point_labels=...)``) are not
+    offered here: the NDT plan's state is overwritten by the next batch's NDT
+    stage before this batch's forward ends, so the points' rows would have to
+    be taken in the NDT stage and carried through the ring with the row
+    blocks.
     """
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,

@@ -152,6 +152,36 @@ class NdtPlan:
                                         None, None, None, self.stats.data_ptr())
         _lib.check(rc, "ndnet_ndt_prune")
 
+    def point_rows(self, points: torch.Tensor, rows_block: Optional[torch.Tensor] = None,
+                   num_nds: Optional[int] = None, fill: str = "none",
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The output row of every input point, int32 ``[B, N]``, after the last
+        ``run`` / ``prune`` of this plan on the same ``points`` (stream
+        ordered; include/ndnet_amd.h ndnet_ndt_point_rows).  A point that
+        contributed to no surviving row gets -1 (``fill="none"``) or the row
+        whose mean is nearest (``fill="nearest"``: ``rows_block`` is the
+        ``[B, num_nds, 12]`` block that level wrote).  ``num_nds``: the NDs of
+        the level last run (default: the plan's)."""
+        assert points.is_contiguous() and points.dtype == torch.float32 and points.device == self.device
+        assert points.shape == (self.batch, self.num_points, 3)
+        if fill not in _lib.POINT_FILL:
+            raise ValueError(f"fill must be 'none' or 'nearest', got {fill!r}")
+        k = self.num_nds if num_nds is None else int(num_nds)
+        if rows_block is not None:
+            assert rows_block.is_contiguous() and rows_block.dtype == torch.float32
+            assert rows_block.device == self.device and rows_block.shape == (self.batch, k, 12)
+        elif fill == "nearest":
+            raise ValueError("fill='nearest' needs the rows block of the level last run")
+        if out is None:
+            out = torch.empty((self.batch, self.num_points), dtype=torch.int32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.int32 and out.device == self.device
+        assert out.shape == (self.batch, self.num_points)
+        rc = _lib.lib().ndnet_ndt_point_rows(self.handle, _lib.stream_ptr(self.device), points.data_ptr(),
+                                             rows_block.data_ptr() if rows_block is not None else None, k,
+                                             _lib.POINT_FILL[fill], out.data_ptr())
+        _lib.check(rc, "ndnet_ndt_point_rows")
+        return out
+
     def host_stats(self) -> list:
         raw = self.stats.cpu().numpy().tobytes()
         return [_lib.NdtStats.from_buffer_copy(raw, i * _lib.STATS_BYTES) for i in range(self.batch)]
@@ -255,6 +285,7 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
         out_cls = torch.empty((B, num_nds, ncls + 1), dtype=torch.float32, device=dev)
     plan.run(pts, labels, out, out_cls)
     ndt_preprocessing.last_plan = plan
+    ndt_preprocessing.last_rows = out  # the device block (ndnet.segment.point_rows reads it)
     if (CHECK_RC if check is None else check) and not torch.cuda.is_current_stream_capturing():
         check_stats(plan)
     if src_device != dev:
@@ -264,6 +295,7 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
 
 
 ndt_preprocessing.last_plan = None
+ndt_preprocessing.last_rows = None
 
 
 def ndt_multiscale(levels, points: torch.Tensor, classes: torch.Tensor = None, num_classes: int = None) -> list:
@@ -286,6 +318,7 @@ def ndt_multiscale(levels, points: torch.Tensor, classes: torch.Tensor = None, n
         blk = torch.empty((B, k, 12), dtype=torch.float32, device=dev)
         blk_cls = torch.empty((B, k, cls.shape[2]), dtype=torch.float32, device=dev) if cls is not None else None
         plan.prune(k, blk, blk_cls)
+        ndt_preprocessing.last_rows = blk  # the last level's block, as ndt_preprocessing keeps its own
         if points.device != dev:
             blk = blk.to(points.device)
             blk_cls = blk_cls.to(points.device) if blk_cls is not None else None

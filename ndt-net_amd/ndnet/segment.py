@@ -1,0 +1,117 @@
+"""Per-point segmentation labels: the ND predictions mapped back to the points.
+
+``ndt_preprocessing`` folds ``[B, N, 3]`` points into ``[B, k, 12]`` normal
+distributions and ``NDTNetSegmentation`` scores one row per ND.  The row every
+point was folded into comes from the NDT plan itself (``ndnet_ndt_point_rows``,
+include/ndnet_amd.h: the kernels' own voxel keys, dense ids and survivor
+numbering), the class of every row and the gather to the points from
+include/ndnet_segment.h.  All of it runs on the GPU in HIP kernels; ``iou`` is
+plain torch.
+
+    labels, log_probs = segment_points(model, 1000, points)       # [B, N] int32
+    conf = confusion(labels, gt, model.num_classes)               # [C + 1, C + 1]
+    per_class, mean = iou(conf)
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from .preprocessing.ndtnet_preprocessing import NdtPlan, ndt_preprocessing
+
+
+def point_rows(points: torch.Tensor, fill: str = "none", plan: Optional[NdtPlan] = None,
+               rows_block: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The output row of every point of ``points`` ``[B, N, 3]``, int32
+    ``[B, N]``: -1 (``fill="none"``) or the nearest row (``fill="nearest"``)
+    for a point that contributed to no surviving ND.  ``plan`` defaults to the
+    plan of the last ``ndt_preprocessing`` / ``ndt_multiscale`` call and
+    ``rows_block`` to the ``[B, k, 12]`` block it returned (its last level's);
+    ``points`` must be the points that call ran on."""
+    _lib.require_gpu()
+    if plan is None:
+        plan = ndt_preprocessing.last_plan
+        if plan is None:
+            raise RuntimeError("point_rows needs a plan: call ndt_preprocessing first")
+        if rows_block is None:
+            rows_block = ndt_preprocessing.last_rows
+    pts = points.to(device=plan.device, dtype=torch.float32).contiguous()
+    k = rows_block.shape[1] if rows_block is not None else None
+    return plan.point_rows(pts, rows_block, k, fill, out)
+
+
+def point_labels(scores: torch.Tensor, rows: torch.Tensor, unassigned: int = -1,
+                 out: Optional[torch.Tensor] = None, nd_labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``labels[b, i] = argmax(scores[b, rows[b, i]])``, int32 ``[B, N]``;
+    ``unassigned`` where ``rows[b, i] < 0``.  ``scores`` ``[B, k, C + 1]``
+    float32 (log-probs or any per-ND scores), ``rows`` ``[B, N]`` int32.  The
+    argmax runs once per ND (first maximum, NaN as a maximum, as
+    ``torch.argmax``); ``nd_labels`` ``[B, k]`` int32 receives it."""
+    _lib.require_gpu()
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3
+    assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.device == scores.device
+    assert rows.shape[0] == scores.shape[0]
+    scores, rows = scores.contiguous(), rows.contiguous()
+    B, k, cols = scores.shape
+    n = rows.shape[1]
+    if out is None:
+        out = torch.empty((B, n), dtype=torch.int32, device=scores.device)
+    if nd_labels is None:
+        nd_labels = torch.empty((B, k), dtype=torch.int32, device=scores.device)
+    for t, shape in ((out, (B, n)), (nd_labels, (B, k))):
+        assert t.is_contiguous() and t.dtype == torch.int32 and t.device == scores.device and t.shape == shape
+    rc = _lib.lib().ndnet_seg_point_labels(scores.data_ptr(), rows.data_ptr(), B, n, k, cols, int(unassigned),
+                                           nd_labels.data_ptr(), out.data_ptr(), _lib.stream_ptr(scores.device))
+    _lib.check(rc, "ndnet_seg_point_labels")
+    return out
+
+
+def segment_points(model, num_nds: int, points: torch.Tensor, fill: str = "nearest"
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A class for every point of ``points`` ``[B, N, 3]``: ``ndt_preprocessing``,
+    ``model`` (an eval-mode ``NDTNetSegmentation``), the points' rows and the
+    rows' classes, eagerly under ``torch.no_grad()``.
+
+    Returns ``(labels [B, N] int32, log_probs [B, num_nds, C + 1])``.  With
+    ``fill="nearest"`` (default) a point that fell into a pruned ND or the
+    ``N % 8`` tail takes the class of the nearest surviving ND; with
+    ``fill="none"`` it gets -1.  Every point of a cloud whose NDT failed gets
+    -1 either way."""
+    with torch.no_grad():
+        p, c, _ = ndt_preprocessing(int(num_nds), points)
+        plan, block = ndt_preprocessing.last_plan, ndt_preprocessing.last_rows
+        log_probs = model(p.to(plan.device), c.to(plan.device))
+        rows = point_rows(points, fill, plan, block)
+        return point_labels(log_probs, rows), log_probs
+
+
+def confusion(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """Point-level confusion matrix ``[C + 1, C + 1]`` int64 (``[gt, pred]``)
+    over every point whose ``pred`` and ``gt`` both lie in ``0 .. num_classes``;
+    other points (unassigned, ignore labels) are left out."""
+    _lib.require_gpu()
+    cols = int(num_classes) + 1
+    assert pred.is_cuda and gt.device == pred.device and pred.numel() == gt.numel() and pred.numel() > 0
+    p = pred.to(torch.int32).contiguous()
+    g = gt.to(torch.int32).contiguous()
+    conf = torch.zeros(cols * cols + 1, dtype=torch.int64, device=pred.device)
+    rc = _lib.lib().ndnet_seg_confusion(p.data_ptr(), g.data_ptr(), p.numel(), cols, conf.data_ptr(),
+                                        _lib.stream_ptr(pred.device))
+    _lib.check(rc, "ndnet_seg_confusion")
+    return conf[:-1].view(cols, cols)
+
+
+def iou(conf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-class intersection over union of a ``[gt, pred]`` confusion matrix
+    and its mean over the classes with a non-empty union (NaN for the others,
+    and for the mean of an all-zero matrix).  Plain torch: any device."""
+    c = conf.to(torch.float64)
+    tp = c.diagonal()
+    union = c.sum(0) + c.sum(1) - tp
+    per_class = torch.where(union > 0, tp / union.clamp(min=1), torch.full_like(tp, float("nan")))
+    seen = union > 0
+    mean = per_class[seen].mean() if bool(seen.any()) else torch.tensor(float("nan"), dtype=torch.float64,
+                                                                         device=conf.device)
+    return per_class, mean
