@@ -21,6 +21,9 @@ NDNET_ERR_HIP = -21
 NDNET_ERR_SYNC = -22
 POINT_FILL = {"none": 0, "nearest": 1}  # NDNET_POINT_FILL_* (include/ndnet_amd.h)
 SEG_CONF_LDS_MAX_COLS = 63  # NDNET_SEG_CONF_LDS_MAX_COLS (include/ndnet_segment.h)
+FPS_THREADS = 512  # NDNET_FPS_* (include/ndnet_fps.h)
+FPS_LDS_POINTS = {"float32": 12288, "float64": 6144}
+FPS_REG_POINTS = {"float32": 100352, "float64": 49152}
 
 
 class NdtStats(ctypes.Structure):
@@ -88,6 +91,9 @@ EXPORTS = {
     # include/ndnet_segment.h
     "ndnet_seg_point_labels": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_int32, _P, _P, _P]),
     "ndnet_seg_confusion": (_I, [_P, _P, _U64, _I, _P, _P]),
+    # include/ndnet_fps.h
+    "ndnet_fps_run": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
+    "ndnet_fps_run_f64": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
     "ndnet_ndt_debug_dump": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_debug_set_epoch": (_I, [_P, ctypes.c_uint32]),
     "ndnet_ndt_debug_set_kl_fuse": (_I, [_P, _I]),

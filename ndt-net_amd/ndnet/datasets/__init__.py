@@ -1,1 +1,1 @@
-from .carla_seg import CARLA_Seg  # noqa: F401
+from .carla_seg import CARLA_Seg, collate_padded  # noqa: F401

@@ -10,6 +10,13 @@ points, and a one-hot ``[n_samples, n_classes + 1]`` ground truth.  For the
 same RNG state it returns the reference's tensors exactly
 (tests/test_ingest.py against oracle/ingest_oracle.py).
 
+``CARLA_Seg(n_classes, None, path)`` returns whole scans instead -- float32
+points ``[m, 3]`` and class ids ``[m]`` int64, no random choice and no
+one-hot -- and ``collate_padded`` pads such ragged scans into one batch with
+its ``counts``; on the GPU ``ndnet.preprocessing.fps_downsample`` then makes
+the fixed-size batch by farthest point sampling, the data path the
+reference's docstrings describe ("using FPS").
+
 ``loader()`` pipelines ingest with the GPU: DataLoader worker processes parse
 scans while the GPU runs the previous batch, into pinned host memory
 (train.py:134-137 uses 4 workers + pin_memory), and the H2D copy is
@@ -19,7 +26,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -52,7 +59,7 @@ def read_ply(path: str, num_classes: int, num_header_lines: int = 10, threads: i
 class CARLA_Seg(Dataset):
     """Same constructor, methods and outputs as the reference's CARLA_Seg."""
 
-    def __init__(self, n_classes: int, n_samples: int, path: str) -> None:
+    def __init__(self, n_classes: int, n_samples: Optional[int], path: str) -> None:
         super().__init__()
         self.n_classes: int = n_classes
         self.n_samples = n_samples
@@ -80,6 +87,8 @@ class CARLA_Seg(Dataset):
 
     def get_data_pcl(self, pcl_filename: str, num_header_lines: int = 10, threads: int = 0):
         xyz, cls = read_ply(pcl_filename, self.n_classes, num_header_lines, threads)
+        if self.n_samples is None:  # the whole scan, for collate_padded and a sampler on the GPU
+            return torch.from_numpy(xyz).float(), torch.from_numpy(cls.astype(np.int64))
         idx = np.random.choice(xyz.shape[0], self.n_samples, replace=False)  # CARLA_Seg.py:137-138
         points = torch.from_numpy(xyz[idx]).float()
         gt = torch.zeros((self.n_samples, self.n_classes + 1), dtype=torch.float32)
@@ -87,8 +96,25 @@ class CARLA_Seg(Dataset):
         return points, gt
 
 
-def loader(dataset: Dataset, batch_size: int, shuffle: bool = True, num_workers: int = 4):
+def collate_padded(batch) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Whole scans of different lengths (``CARLA_Seg(n_classes, None, path)``
+    items: points ``[m, 3]``, class ids ``[m]``) as one batch: ``(points
+    [B, n_max, 3] float32, classes [B, n_max] int64, counts [B] int32)``.
+    Padding points and padding classes are 0."""
+    counts = torch.tensor([len(p) for p, _ in batch], dtype=torch.int32)
+    n_max = int(counts.max())
+    points = torch.zeros((len(batch), n_max, 3), dtype=torch.float32)
+    classes = torch.zeros((len(batch), n_max), dtype=torch.int64)
+    for b, (p, c) in enumerate(batch):
+        points[b, :len(p)] = p
+        classes[b, :len(c)] = c
+    return points, classes, counts
+
+
+def loader(dataset: Dataset, batch_size: int, shuffle: bool = True, num_workers: int = 4, collate_fn=None):
     """DataLoader as train.py:134-137 builds it: worker processes parse ahead
-    of the GPU, batches land in pinned memory for non-blocking H2D copies."""
+    of the GPU, batches land in pinned memory for non-blocking H2D copies.
+    ``collate_fn=collate_padded`` batches whole scans of different lengths."""
     return torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, pin_memory=True,
-                                       num_workers=num_workers, persistent_workers=num_workers > 0)
+                                       num_workers=num_workers, persistent_workers=num_workers > 0,
+                                       collate_fn=collate_fn)

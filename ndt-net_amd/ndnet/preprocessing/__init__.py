@@ -1,2 +1,3 @@
+from .fps import farthest_point_sample, fps_downsample  # noqa: F401
 from .ndt_legacy import NDT_Sampler  # noqa: F401
 from .ndtnet_preprocessing import ndt_preprocessing  # noqa: F401
