@@ -231,6 +231,32 @@ int ndnet_ndt_run_f64(void *plan, void *stream, const double *d_points, const in
                       double *d_out_points, double *d_out_covariances, uint16_t *d_out_classes, float *d_out,
                       ndnet_ndt_stats *d_stats);
 
+/* Ragged batches: the same runs with a per-cloud point count.  d_counts:
+ * [batch] int32 on the device, or NULL (then these are ndnet_ndt_run /
+ * ndnet_ndt_run_f64, which are their NULL case).  Cloud b consists of its
+ * first d_counts[b] points and nothing else: num_points stays the stride
+ * between clouds (d_points and d_labels are [batch][num_points][..], the plan's
+ * workspaces are sized for it), and everything the reference derives from a
+ * cloud's size -- the eight workers' chunk d_counts[b] / 8, the d_counts[b] % 8
+ * tail the estimation ignores and the limits include, the workers' cut-offs,
+ * the bisection's skip bound -- uses the count.  The cloud's rows, classes and
+ * stats are, bit for bit, those of a run of that cloud alone in a plan of
+ * num_points = d_counts[b].  The points at and past the count (and their
+ * labels) are padding: they may hold anything (NaN, inf), influence no result,
+ * and nothing outside the cloud's [0, num_points) is read.
+ * A cloud with d_counts[b] < 1 or > num_points fails alone: stats rc =
+ * NDNET_ERR_ARG (-20), zero rows, a class-0 one-hot; the batch's other clouds
+ * are unaffected.  The counts are read on the device by the run's kernels (no
+ * allocation, no synchronisation: capturable, and one captured graph serves
+ * any counts written to the same buffer before a replay); d_counts must not
+ * change while a run that reads it is in flight.  With ndnet_ndt_set_run_part,
+ * part 2 takes the same d_counts as part 1. */
+int ndnet_ndt_run_counts(void *plan, void *stream, const float *d_points, const int32_t *d_labels,
+                         const int32_t *d_counts, float *d_out, float *d_out_classes, ndnet_ndt_stats *d_stats);
+int ndnet_ndt_run_f64_counts(void *plan, void *stream, const double *d_points, const int32_t *d_labels,
+                             const int32_t *d_counts, double *d_out_points, double *d_out_covariances,
+                             uint16_t *d_out_classes, float *d_out, ndnet_ndt_stats *d_stats);
+
 /* A further prune level of every cloud of the last run (NDT_Sampler.prune,
  * ndt_legacy.py:173-240): outputs sized [batch][num_desired][...]. */
 int ndnet_ndt_prune(void *plan, void *stream, uint64_t num_desired, float *d_out, float *d_out_classes,
@@ -261,6 +287,14 @@ int ndnet_ndt_prune(void *plan, void *stream, uint64_t num_desired, float *d_out
 #define NDNET_POINT_FILL_NEAREST 1
 int ndnet_ndt_point_rows(void *plan, void *stream, const float *d_points, const float *d_rows_block,
                          uint64_t num_desired, int fill, int32_t *d_point_rows);
+
+/* The same after ndnet_ndt_run_counts, with the d_counts of that run (NULL:
+ * ndnet_ndt_point_rows).  The n % 8 tail and the workers' cut-offs are those of
+ * the cloud's count; a padding point (i >= d_counts[b]) gets -1 under both
+ * fills, whatever it holds, and is never searched for a nearest row; every
+ * point of a cloud with an invalid count gets -1 (the cloud has no rows). */
+int ndnet_ndt_point_rows_counts(void *plan, void *stream, const float *d_points, const float *d_rows_block,
+                                uint64_t num_desired, int fill, int32_t *d_point_rows, const int32_t *d_counts);
 
 /* Stage timing with HIP events on the run's stream (bench.py): after
  * ndnet_ndt_set_timing(plan, 1), each run records events around its stages;

@@ -68,6 +68,7 @@ constexpr int kPhDenseLarge = 36;
 constexpr int kFrontMarkStride = 32 + 2 * 256;  // per cloud: 32 phase stamps of WG 0, then start/end of WG g < 256
 constexpr int kBarStride = 16;      // u32 between the barrier counters of two clouds (64 B)
 constexpr int kNdtErrSync = -22;    // NDNET_ERR_SYNC
+constexpr int kNdtErrArg = -20;     // NDNET_ERR_ARG: a cloud's count outside 1..n
 static_assert(kFrontTable * 4 >= kBitsCap, "the byte map holds a whole small grid");
 
 struct FrontArgs {
@@ -101,6 +102,7 @@ struct FrontArgs {
   uint32_t* lu_done;            // [B][lu_gcap] k_welford_q's group counters, re-armed with the cloud
   uint32_t lu_gcap;
   uint32_t* sync_fail;          // mapped host word: set on a barrier timeout (ndnet_ndt_take_sync_failures), or null
+  const int32_t* counts;        // [B] points of each cloud (k_front<T, true>), or null: n for every cloud
 };
 
 // The shared bisection state of one workgroup (every workgroup of a cloud
@@ -266,7 +268,9 @@ __device__ inline void front_point(const T* p, uint64_t i, T& x, T& y, T& z) {
 constexpr int kFrontXB = NDNET_FRONT_XB;  // bins past kFrontR loaded together
 
 // the points of bins j0 .. j0 + kFrontXB - 1 of this thread (index clamped to
-// the cloud's last point: every load valid, all of them in flight together)
+// the last point of the cloud's stride n: every load valid, all of them in
+// flight together; with per-cloud counts a load past the count reads padding,
+// whose value every user discards)
 template <typename T>
 __device__ inline void front_points_xb(const T* p, uint64_t bin0, uint32_t j0, uint32_t t, uint64_t n,
                                        T (&xs)[kFrontXB], T (&ys)[kFrontXB], T (&zs)[kFrontXB]) {
@@ -289,7 +293,17 @@ __device__ inline void front_points_xb(const T* p, uint64_t bin0, uint32_t j0, u
       A.marks[(uint64_t)b * kFrontMarkStride + 32 + 2 * g + (e)] = __builtin_amdgcn_s_memrealtime();  \
   } while (0)
 
-template <typename T>
+// kRagged: the cloud's point count is A.counts[b] instead of A.n (a second
+// instantiation: with kRagged = false every ragged line below folds away and
+// the fixed-size kernel is the code it was).  A.n stays the stride between
+// clouds (ns) in both; n is the count everything the reference derives from
+// the cloud's size uses.  The always-issued loads clamp to the stride (they stay
+// inside the cloud's [0, A.n) and do not wait for the count; a padding point's
+// value is dropped by the count checks of its users).  The count is the same in
+// all of a cloud's workgroups, so the barriers they reach stay the same too; a
+// count outside 1..A.n runs the cloud through with zero points and fails it
+// (NDNET_ERR_ARG).
+template <typename T, bool kRagged>
 __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ pts, FrontArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t f_smem[];
   __shared__ FrontState s;
@@ -335,9 +349,18 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
   }
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
   CloudCtl& c = A.ctl[b];
-  const uint64_t n = A.n;
+  const uint64_t ns = A.n;
+  const int32_t cb = kRagged ? A.counts[b] : 0;
+  const bool bad_count = kRagged && (cb < 1 || (uint64_t)cb > ns);
+  const uint64_t n = kRagged ? (bad_count ? (uint64_t)0 : (uint64_t)cb) : ns;
   const uint64_t chunk = n / kWorkers, n8 = chunk * kWorkers;
-  const T* p = pts + (uint64_t)b * n * 3;
+  // worker of point i; kRagged: an index past the count (its result is
+  // discarded) must not index s.cut by a quotient of any size
+  auto worker_of = [=](uint64_t i) -> uint64_t {
+    if constexpr (kRagged) return i < n8 ? i / chunk : (uint64_t)0;
+    else return i / chunk;
+  };
+  const T* p = pts + (uint64_t)b * ns * 3;
   uint32_t* bar = A.bar + (uint64_t)b * kBarStride;
   uint32_t* table = f_smem;                                   // kFrontTable words
   uint8_t* bytemap = (uint8_t*)f_smem;                        // small grids: one byte per voxel
@@ -398,7 +421,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
 #pragma unroll
   for (int j = 0; j < kFrontR; j++) {
     const uint64_t i = (bin0 + j) * 1024 + t;
-    const uint64_t ic = i < n ? i : n - 1;
+    const uint64_t ic = i < ns ? i : ns - 1;  // (the stride, not the count: the loads need not wait for the count)
     front_point(p, ic, px[j], py[j], pz[j]);
   }
 #pragma unroll
@@ -415,7 +438,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
   // addresses), not one dependent round trip per bin
   for (uint32_t j0 = kFrontR; j0 < bpw; j0 += kFrontXB) {
     T xs[kFrontXB], ys[kFrontXB], zs[kFrontXB];
-    front_points_xb(p, bin0, j0, t, n, xs, ys, zs);
+    front_points_xb(p, bin0, j0, t, ns, xs, ys, zs);
 #pragma unroll
     for (int u = 0; u < kFrontXB; u++) {
       const uint64_t i = (bin0 + j0 + u) * 1024 + t;
@@ -465,6 +488,10 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
     s.iter = 0;
     s.state = kSearching;
     s.guess = (kMaxGuess - kMinGuess) / 2.0;  // ndt.c:136
+    if (kRagged && bad_count) {  // every workgroup of the cloud alike: no pass, no further barrier
+      s.state = kFailed;
+      s.vs = 0.0;
+    }
   }
   __syncthreads();
 
@@ -499,7 +526,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
         // parity tests that compare every count with the reference's).
         const uint64_t bound = V < n8 ? V : n8;
         s.skip = !A.eval_all && bound < A.k;
-        if (V > A.vcap) {  // the reference's malloc of V NDs would be the failure point
+        if (V > A.vcap && !(kRagged && bad_count)) {  // the reference's malloc of V NDs would be the failure point
           s.state = kFailed;
           s.rc = -1;
           s.vs = s.guess;
@@ -578,7 +605,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
       if ((uint32_t)j < bpw) visit(j, (bin0 + j) * 1024 + t, px[j], py[j], pz[j]);
     for (uint32_t j0 = kFrontR; j0 < bpw; j0 += kFrontXB) {
       T xs[kFrontXB], ys[kFrontXB], zs[kFrontXB];
-      front_points_xb(p, bin0, j0, t, n, xs, ys, zs);
+      front_points_xb(p, bin0, j0, t, ns, xs, ys, zs);
 #pragma unroll
       for (int u = 0; u < kFrontXB; u++)
         if (j0 + u < bpw) visit(j0 + u, (bin0 + j0 + u) * 1024 + t, xs[u], ys[u], zs[u]);  // (visit checks iend8)
@@ -603,7 +630,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
         const uint64_t i = (bin0 + j) * 1024 + t;
         const uint32_t key = binfo[j * 1024 + t];
         if (i >= iend8) continue;
-        if (key == kInvalid) atomicMin(&s_bad[i / chunk], (uint32_t)i);
+        if (key == kInvalid) atomicMin(&s_bad[worker_of(i)], (uint32_t)i);
         else if (!small) fresh += stamp_key_front(key, table, stamps, stamp);
       }
     }
@@ -664,7 +691,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
       for (uint32_t j = 0; j < bpw; j++) {
         const uint64_t i = (bin0 + j) * 1024 + t;
         const uint32_t key = binfo[j * 1024 + t];
-        if (key != kInvalid && i < s.cut[i / chunk]) f2 += stamp_key_front(key, table, stamps, stamp2);
+        if (key != kInvalid && i < s.cut[worker_of(i)]) f2 += stamp_key_front(key, table, stamps, stamp2);
       }
       f2 = block_sum_u32(f2, scratch);
       uint32_t* rec2 = A.rec + (((uint64_t)b * kFrontPhases + 2 + 2 * s.iter) * G) * kRecWords;
@@ -720,13 +747,14 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
     c.lo = s.lo;
     c.hi = s.hi;
     c.vs = s.vs;
+    const bool no_grid = kRagged && bad_count;  // a refused count: no grid, as the one-launch-per-stage path reports it
     for (int a = 0; a < 3; a++) {
-      c.len[a] = s.len[a];
-      c.off[a] = s.off[a];
+      c.len[a] = no_grid ? 0u : s.len[a];
+      c.off[a] = no_grid ? 0.0 : s.off[a];
     }
-    c.V = s.V;
+    c.V = no_grid ? 0u : s.V;
     c.state = s.state;
-    c.rc = s.rc;
+    c.rc = kRagged && bad_count ? kNdtErrArg : s.rc;
     c.iter = s.iter;
     c.stamp = s.stamp;
     c.accepted_stamp = s.stamp;
@@ -834,7 +862,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
         if ((uint32_t)j < bpw) {
           const uint64_t i = (bin0 + j) * 1024 + t;
           bool ok = keys[j] != kInvalid;
-          if (cuts) ok = ok && i < s.cut[i / chunk];
+          if (cuts) ok = ok && i < s.cut[worker_of(i)];
           binfo[j * 1024 + t] = ok ? dv[j] : kInvalid;
         }
       }
@@ -843,7 +871,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
       const uint64_t i = (bin0 + j) * 1024 + t;
       const uint32_t key = binfo[j * 1024 + t];
       uint32_t d = kInvalid;
-      if (key != kInvalid && i < s.cut[i / chunk]) {
+      if (key != kInvalid && i < s.cut[worker_of(i)]) {
         if (bitmap) {
           const uint32_t bw = bits_l[key >> 5];
           d = pref_l[key >> 5] + __popc(bw & ((1u << (key & 31)) - 1u));
@@ -1036,7 +1064,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
     }
     FRONT_MARK(25);
     // ---- scatter: every point to its ND's run, in index order ----
-    T* out = (T*)A.nd_pts + (uint64_t)b * n * 3;
+    T* out = (T*)A.nd_pts + (uint64_t)b * ns * 3;
     const uint32_t rsub = t / rbs;  // my rank bin within a 1024-point bin
     if constexpr (sizeof(T) == 4) {
       if (staged) {
@@ -1059,7 +1087,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
               const uint32_t d = bi >> 10;
               gd[j] = addv[d] + hist[(uint64_t)(j * (1024 / rbs) + rsub) * ndcap + d] + (bi & 1023u);
               lp[j] = gd[j] - delta[d];
-              if (A.nd_lbl) A.nd_lbl[(uint64_t)b * n + gd[j]] = (uint16_t)A.lbl[(uint64_t)b * n + (bin0 + j) * 1024 + t];
+              if (A.nd_lbl) A.nd_lbl[(uint64_t)b * ns + gd[j]] = (uint16_t)A.lbl[(uint64_t)b * ns + (bin0 + j) * 1024 + t];
             }
           }
         }
@@ -1107,14 +1135,14 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
         o[1] = y;
         o[2] = z;
       }
-      if (A.nd_lbl) A.nd_lbl[(uint64_t)b * n + dst] = (uint16_t)A.lbl[(uint64_t)b * n + i];
+      if (A.nd_lbl) A.nd_lbl[(uint64_t)b * ns + dst] = (uint16_t)A.lbl[(uint64_t)b * ns + i];
     };
 #pragma unroll
     for (int j = 0; j < kFrontR; j++)
       if ((uint32_t)j < bpw) put(j, (bin0 + j) * 1024 + t, px[j], py[j], pz[j]);
     for (uint32_t j0 = kFrontR; j0 < bpw; j0 += kFrontXB) {
       T xs[kFrontXB], ys[kFrontXB], zs[kFrontXB];
-      front_points_xb(p, bin0, j0, t, n, xs, ys, zs);
+      front_points_xb(p, bin0, j0, t, ns, xs, ys, zs);
 #pragma unroll
       for (int u = 0; u < kFrontXB; u++) {
         const uint64_t i = (bin0 + j0 + u) * 1024 + t;

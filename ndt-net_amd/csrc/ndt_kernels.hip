@@ -5,6 +5,9 @@
 // with batched HIP kernels.  One batch = B clouds of n points; every kernel
 // covers the whole batch, so the per-cloud latency chain (up to 15 voxel-size
 // bisection passes) is paid once per batch, not once per cloud.
+// A run may also take per-cloud point counts (ndnet_ndt_run_counts): n is then
+// the stride between clouds and cloud b its first counts[b] points (DESIGN.md
+// §3 "Ragged batches").
 //
 // Kernels, in launch order (see DESIGN.md for the data layout and rooflines):
 //   k_reset        per-cloud control block for this call
@@ -374,19 +377,31 @@ __device__ inline bool arrive_ticket(uint32_t* arrive, uint32_t G) {
 
 constexpr int kLimPPT = 16;        // flat coordinates per thread in k_limits
 
+// Ragged batches: the points cloud b has -- counts[b], or the plan's n (the
+// stride between clouds) when counts is null: a uniform branch on the pointer,
+// one scalar load per workgroup.  A count outside 1..n gives 0: the cloud runs
+// through with no point and k_limits fails it (NDNET_ERR_ARG).
+__device__ inline uint64_t cloud_points(const int32_t* __restrict__ counts, int b, uint64_t n) {
+  if (!counts) return n;
+  const int32_t cb = counts[b];
+  return cb < 1 || (uint64_t)cb > n ? 0u : (uint64_t)cb;
+}
+
 // Bounding box (pointclouds.c:40-66) over every point, the n % 8 tail
 // included.  Coordinates are read as a flat, coalesced stream; element f is
 // axis f % 3.
 template <typename T>
 __global__ void __launch_bounds__(256) k_limits(const T* __restrict__ pts, CloudCtl* ctl, uint32_t* gbits_all,
-                                                uint32_t* stamps, uint64_t n, uint32_t G, uint64_t vcap) {
+                                                uint32_t* stamps, uint64_t n, uint32_t G, uint64_t vcap,
+                                                const int32_t* __restrict__ counts) {
   const int b = blockIdx.y;
+  const uint64_t nc = cloud_points(counts, b, n);
   if (ctl[b].clear_stamps) {  // epoch wrap (k_reset): rare, cost irrelevant
     uint32_t* sb = stamps + (uint64_t)b * vcap;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < vcap; i += (uint64_t)G * 256) sb[i] = 0;
   }
   const T* p = pts + (uint64_t)b * n * 3;
-  const uint64_t nf = 3 * n;
+  const uint64_t nf = 3 * nc;
   double mx[3] = {kDblMin, kDblMin, kDblMin}, mn[3] = {kDblMax, kDblMax, kDblMax};
   const uint64_t f0 = (uint64_t)blockIdx.x * 256 * kLimPPT + threadIdx.x;
   T v[kLimPPT];
@@ -440,7 +455,12 @@ __global__ void __launch_bounds__(256) k_limits(const T* __restrict__ pts, Cloud
     c.arrive = 0;
     c.lo = kMinGuess;
     c.hi = kMaxGuess;
-    set_guess(c, (kMaxGuess - kMinGuess) / 2.0, vcap);  // ndt.c:136
+    if (nc == 0) {  // a count outside 1..n
+      c.state = kFailed;
+      c.rc = NDNET_ERR_ARG;
+    } else {
+      set_guess(c, (kMaxGuess - kMinGuess) / 2.0, vcap);  // ndt.c:136
+    }
   }
   __syncthreads();
   if (c.state == kSearching && c.V <= (uint64_t)kBitsCap) {  // clear pass 0's occupancy bitmap
@@ -518,7 +538,7 @@ template <typename T>
 __global__ void __launch_bounds__(kPassThreads) k_search_pass(const T* __restrict__ pts, CloudCtl* ctl,
                                                               uint32_t* stamps_all, uint32_t* gbits_all,
                                                               uint32_t* keys_all, uint64_t n, uint64_t k, uint32_t G,
-                                                              uint64_t vcap) {
+                                                              uint64_t vcap, const int32_t* __restrict__ counts) {
   const int b = blockIdx.y;
   CloudCtl& c = ctl[b];
   if (__hip_atomic_load(&c.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kSearching) return;
@@ -526,7 +546,7 @@ __global__ void __launch_bounds__(kPassThreads) k_search_pass(const T* __restric
   __shared__ uint32_t table[kHashSlots];  // LDS bitmap (small grids) or hash table
   __shared__ uint32_t scratch[16];
   __shared__ uint32_t last;
-  const uint64_t chunk = n / kWorkers;       // pcl_worker range, normal_distributions.c:34-35
+  const uint64_t chunk = cloud_points(counts, b, n) / kWorkers;  // pcl_worker range, normal_distributions.c:34-35
   const uint64_t n8 = chunk * kWorkers;      // the n % 8 tail is never estimated
   const T* p = pts + (uint64_t)b * n * 3;
   uint32_t* stamps = stamps_all + (uint64_t)b * vcap;
@@ -694,7 +714,8 @@ constexpr int kBinThreads = 256;
 __global__ void __launch_bounds__(kBinThreads) k_bin_count(const CloudCtl* ctl, const uint32_t* __restrict__ keys_all,
                                                            const uint32_t* __restrict__ dense_all, uint32_t* did_all,
                                                            uint32_t* counts_all, uint64_t n, uint64_t vcap,
-                                                           uint32_t ndcap, uint32_t nbins) {
+                                                           uint32_t ndcap, uint32_t nbins,
+                                                           const int32_t* __restrict__ counts) {
   const int b = blockIdx.y, ch = blockIdx.x;
   const CloudCtl& c = ctl[b];
   if (c.state != kAccepted) return;
@@ -702,13 +723,14 @@ __global__ void __launch_bounds__(kBinThreads) k_bin_count(const CloudCtl* ctl, 
   const uint32_t nd = c.num_nds;
   for (uint32_t d = threadIdx.x; d < nd; d += blockDim.x) hist[d] = 0;
   __syncthreads();
-  const uint64_t chunk = n / kWorkers, n8 = chunk * kWorkers;
+  const uint64_t nc = cloud_points(counts, b, n);
+  const uint64_t chunk = nc / kWorkers, n8 = chunk * kWorkers;
   const uint32_t* dense = dense_all + (uint64_t)b * vcap;
   const uint64_t base = (uint64_t)ch * kBinPts;
 #pragma unroll
   for (int q = 0; q < kBinPts / kBinThreads; q++) {
     const uint64_t i = base + threadIdx.x + kBinThreads * q;
-    if (i >= n) continue;
+    if (i >= nc) continue;
     uint32_t d = kInvalid;
     if (i < n8 && i < c.first_bad[i / chunk]) {
       const uint32_t key = keys_all[(uint64_t)b * n + i];
@@ -787,18 +809,19 @@ __global__ void __launch_bounds__(kBinThreads) k_bin_scatter(const T* __restrict
                                                              const CloudCtl* ctl, const uint32_t* __restrict__ did_all,
                                                              const uint32_t* __restrict__ offs_all, T* nd_pts,
                                                              uint16_t* nd_lbl, uint64_t n, uint32_t ndcap,
-                                                             uint32_t nbins) {
+                                                             uint32_t nbins, const int32_t* __restrict__ counts) {
   const int b = blockIdx.y, ch = blockIdx.x;
   const CloudCtl& c = ctl[b];
   if (c.state != kAccepted) return;
   __shared__ uint32_t skey[kBinPts];
   __shared__ uint32_t scratch[16];
   const uint64_t base = (uint64_t)ch * kBinPts;
+  const uint64_t nc = cloud_points(counts, b, n);  // (did_all holds this run's ids below the count only)
 #pragma unroll
   for (int q = 0; q < kBinPts / kBinThreads; q++) {
     const uint32_t t = threadIdx.x + kBinThreads * q;
     const uint64_t i = base + t;
-    const uint32_t d = i < n ? did_all[(uint64_t)b * n + i] : kInvalid;
+    const uint32_t d = i < nc ? did_all[(uint64_t)b * n + i] : kInvalid;
     skey[t] = d == kInvalid ? kInvalid : (d << 10) | t;
   }
   __syncthreads();
@@ -4438,17 +4461,24 @@ static int front_lanes_finish(Plan* P, hipStream_t st) {
 }
 
 template <typename T>
+static void front_kernel(Plan* P, hipStream_t st, const T* pts, const FrontArgs& F) {
+  // grid, workgroups per cloud and LDS are the plan's, with or without counts
+  if (F.counts) k_front<T, true><<<P->fG * P->B, kFrontThreads, P->flds, st>>>(pts, F);
+  else k_front<T, false><<<P->fG * P->B, kFrontThreads, P->flds, st>>>(pts, F);
+}
+
+template <typename T>
 static int front_launch(Plan* P, hipStream_t st, const T* pts, const FrontArgs& F) {
   P->lane_rec = 0;
   if (!lanes_enabled()) {
-    k_front<T><<<P->fG * P->B, kFrontThreads, P->flds, st>>>(pts, F);
+    front_kernel<T>(P, st, pts, F);
     HIPCHK(hipGetLastError());
     return NDNET_OK;
   }
   std::lock_guard<std::mutex> lk(g_lane_mu);  // waits and launch in one host order
   FrontLaneSet& L = g_lanes[P->dev];
   if (!admission_needed(P, L)) {
-    k_front<T><<<P->fG * P->B, kFrontThreads, P->flds, st>>>(pts, F);
+    front_kernel<T>(P, st, pts, F);
     HIPCHK(hipGetLastError());
     return NDNET_OK;
   }
@@ -4471,7 +4501,7 @@ static int front_launch(Plan* P, hipStream_t st, const T* pts, const FrontArgs& 
     if (!cap) HIPCHK(hipStreamWaitEvent(st, ev, 0));
     else if (nodes) HIPCHK(capture_event_node(st, ev, true));
   }
-  k_front<T><<<P->fG * P->B, kFrontThreads, P->flds, st>>>(pts, F);
+  front_kernel<T>(P, st, pts, F);
   HIPCHK(hipGetLastError());
   if (rec_at_end()) {
     P->lane_rec = 1;
@@ -4491,8 +4521,8 @@ static size_t wq_hist_lds(const Plan* P, bool l64) {
 static void wq_pick_form(Plan* P) { P->wq_l64 = P->wq_form == 1 ? 1 : P->wq_form == 2 ? 0 : (P->cu_share > 1); }
 
 template <typename T>
-static int run_impl(Plan* P, hipStream_t st, const T* pts, const int32_t* lbl, float* out, float* out_cls,
-                    double* pc64, double* cov64, uint16_t* cls16, ndnet_ndt_stats* stats_dst) {
+static int run_impl(Plan* P, hipStream_t st, const T* pts, const int32_t* lbl, const int32_t* counts, float* out,
+                    float* out_cls, double* pc64, double* cov64, uint16_t* cls16, ndnet_ndt_stats* stats_dst) {
   const int B = P->B;
   const uint64_t n = P->n;
   if (lbl && P->ncls < 0) return NDNET_ERR_ARG;
@@ -4506,6 +4536,7 @@ static int run_impl(Plan* P, hipStream_t st, const T* pts, const int32_t* lbl, f
     FrontArgs F;
     F.ctl = P->ctl;
     F.lbl = lbl;
+    F.counts = counts;
     F.stamps = P->stamps;
     F.gbits = P->gbits;
     F.dense_of = P->dense_of;
@@ -4550,21 +4581,21 @@ static int run_impl(Plan* P, hipStream_t st, const T* pts, const int32_t* lbl, f
       for (int e = 1; e <= 4; e++) HIPCHK(hipEventRecord(P->ev[e], st));
   } else {
   const uint32_t Gl = (uint32_t)((3 * n + 256 * kLimPPT - 1) / (256 * kLimPPT));
-  k_limits<T><<<dim3(Gl, B), 256, 0, st>>>(pts, P->ctl, P->gbits, P->stamps, n, Gl, P->vcap);
+  k_limits<T><<<dim3(Gl, B), 256, 0, st>>>(pts, P->ctl, P->gbits, P->stamps, n, Gl, P->vcap, counts);
   if (P->timing) HIPCHK(hipEventRecord(P->ev[1], st));
   for (int it = 0; it < kMaxIters; it++)
     k_search_pass<T><<<dim3(P->G, B), kPassThreads, 0, st>>>(pts, P->ctl, P->stamps, P->gbits, P->pkeys, n, P->k,
-                                                              P->G, P->vcap);
+                                                              P->G, P->vcap, counts);
   if (P->timing) HIPCHK(hipEventRecord(P->ev[2], st));
   k_dense<<<B, 1024, 0, st>>>(P->ctl, P->stamps, P->gbits, P->dense_of, P->vox, P->vcap, P->ndcap);
   if (P->timing) HIPCHK(hipEventRecord(P->ev[3], st));
   k_bin_count<<<dim3(P->nbins, B), kBinThreads, P->ndcap * sizeof(uint32_t), st>>>(
-      P->ctl, P->pkeys, P->dense_of, P->did, P->bin_cnt, n, P->vcap, P->ndcap, P->nbins);
+      P->ctl, P->pkeys, P->dense_of, P->did, P->bin_cnt, n, P->vcap, P->ndcap, P->nbins, counts);
   k_bin_offsets<<<B, 1024, 0, st>>>(P->ctl, P->bin_cnt, P->nd_n, P->nd_base, P->heavy, P->heavy_t, P->ndcap,
                                      P->nbins);
   k_bin_scatter<T><<<dim3(P->nbins, B), kBinThreads, 0, st>>>(pts, lbl, P->ctl, P->did, P->bin_cnt,
                                                                (T*)P->nd_pts, lbl ? P->nd_lbl : nullptr, n,
-                                                               P->ndcap, P->nbins);
+                                                               P->ndcap, P->nbins, counts);
   if (P->timing) HIPCHK(hipEventRecord(P->ev[4], st));
   }
   if (P->run_part == 1) {
@@ -4648,7 +4679,8 @@ __global__ void __launch_bounds__(kPrThreads) k_point_rows(const float* __restri
                                                           const uint32_t* __restrict__ vox_all,
                                                           const uint8_t* __restrict__ alive_all,
                                                           const float* __restrict__ rows_block, int32_t* __restrict__ out,
-                                                          uint64_t n, uint32_t ndcap, uint64_t kdes, int fill) {
+                                                          uint64_t n, uint32_t ndcap, uint64_t kdes, int fill,
+                                                          const int32_t* __restrict__ counts) {
   extern __shared__ __attribute__((aligned(16))) uint32_t pr_smem[];
   __shared__ uint32_t scratch[16];
   __shared__ uint32_t s_cut[kWorkers];
@@ -4725,13 +4757,17 @@ __global__ void __launch_bounds__(kPrThreads) k_point_rows(const float* __restri
   const float lmax = fmaxf(lenf[0], fmaxf(lenf[1], lenf[2]));
   const float half_tol = 0.5f - lmax * 0x1p-19f;
   const bool fast32 = (double)off32[0] == off[0] && (double)off32[1] == off[1] && (double)off32[2] == off[2];
-  const uint64_t chunk = n / kWorkers, n8 = chunk * kWorkers;
+  // ragged batches: the cloud's own count for the tail and the workers (a
+  // cloud with rows has a valid count); a point at or past it is padding --
+  // whatever it holds, it gets -1 and never joins the nearest list
+  const uint64_t nc = cloud_points(counts, b, n);
+  const uint64_t chunk = nc / kWorkers, n8 = chunk * kWorkers;
 #pragma unroll
   for (int q = 0; q < kPrPPT; q++) {
     const uint32_t il = t + kPrThreads * q;
     const uint64_t i = start + il;
     const float x = sp[3 * il], y = sp[3 * il + 1], z = sp[3 * il + 2];
-    const bool finite = isfinite(x) && isfinite(y) && isfinite(z);
+    const bool finite = i < nc && isfinite(x) && isfinite(y) && isfinite(z);
     // a point of the run is never below the grid offset (the cloud's minimum); one that is
     // (a caller's other points) takes the double path, which finds it out of grid
     const bool below = x < off32[0] || y < off32[1] || z < off32[2];
@@ -4853,12 +4889,18 @@ hipError_t front_config(Plan* P, int share) {
   hipError_t e = hipSuccess;
   // (addv, the per-ND base words of the binning, live in the table region)
   int ok = lds <= 150 * 1024 && (G == 1 || (uint64_t)G * B <= (uint64_t)cus) && P->ndcap <= (uint32_t)kFrontTable;
-  if (ok) e = hipFuncSetAttribute((const void*)k_front<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  if (ok && e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_front<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+  const void* fronts[4] = {(const void*)k_front<float, false>, (const void*)k_front<double, false>,
+                           (const void*)k_front<float, true>, (const void*)k_front<double, true>};
+  for (int i = 0; i < 4 && ok && e == hipSuccess; i++)
+    e = hipFuncSetAttribute(fronts[i], hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
   if (ok && e == hipSuccess) {
     int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_front<double>, kFrontThreads, lds);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_front<double, false>, kFrontThreads, lds);
+    if (e == hipSuccess && nb < 1) ok = 0;
+  }
+  if (ok && e == hipSuccess) {
+    int nb = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_front<double, true>, kFrontThreads, lds);
     if (e == hipSuccess && nb < 1) ok = 0;
   }
   P->fG = G;
@@ -5188,24 +5230,36 @@ int ndnet_ndt_stage_ms(void* plan, float* ms) {
   return NDNET_OK;
 }
 
-int ndnet_ndt_run(void* plan, void* stream, const float* d_points, const int32_t* d_labels, float* d_out,
-                  float* d_out_classes, ndnet_ndt_stats* d_stats) {
+int ndnet_ndt_run_counts(void* plan, void* stream, const float* d_points, const int32_t* d_labels,
+                         const int32_t* d_counts, float* d_out, float* d_out_classes, ndnet_ndt_stats* d_stats) {
   Plan* P = (Plan*)plan;
   if (!P || !d_points) return NDNET_ERR_ARG;
   if (d_labels && P->ncls < 0) return NDNET_ERR_ARG;
   P->in_f64 = 0;
-  return run_impl<float>(P, (hipStream_t)stream, d_points, d_labels, d_out, d_out_classes, nullptr, nullptr,
+  return run_impl<float>(P, (hipStream_t)stream, d_points, d_labels, d_counts, d_out, d_out_classes, nullptr, nullptr,
                          nullptr, d_stats);
 }
 
-int ndnet_ndt_run_f64(void* plan, void* stream, const double* d_points, const int32_t* d_labels, double* d_out_points,
-                      double* d_out_covariances, uint16_t* d_out_classes, float* d_out, ndnet_ndt_stats* d_stats) {
+int ndnet_ndt_run(void* plan, void* stream, const float* d_points, const int32_t* d_labels, float* d_out,
+                  float* d_out_classes, ndnet_ndt_stats* d_stats) {
+  return ndnet_ndt_run_counts(plan, stream, d_points, d_labels, nullptr, d_out, d_out_classes, d_stats);
+}
+
+int ndnet_ndt_run_f64_counts(void* plan, void* stream, const double* d_points, const int32_t* d_labels,
+                             const int32_t* d_counts, double* d_out_points, double* d_out_covariances,
+                             uint16_t* d_out_classes, float* d_out, ndnet_ndt_stats* d_stats) {
   Plan* P = (Plan*)plan;
   if (!P || !d_points) return NDNET_ERR_ARG;
   if (d_labels && P->ncls < 0) return NDNET_ERR_ARG;
   P->in_f64 = 1;
-  return run_impl<double>(P, (hipStream_t)stream, d_points, d_labels, d_out, nullptr, d_out_points,
+  return run_impl<double>(P, (hipStream_t)stream, d_points, d_labels, d_counts, d_out, nullptr, d_out_points,
                           d_out_covariances, d_out_classes, d_stats);
+}
+
+int ndnet_ndt_run_f64(void* plan, void* stream, const double* d_points, const int32_t* d_labels, double* d_out_points,
+                      double* d_out_covariances, uint16_t* d_out_classes, float* d_out, ndnet_ndt_stats* d_stats) {
+  return ndnet_ndt_run_f64_counts(plan, stream, d_points, d_labels, nullptr, d_out_points, d_out_covariances,
+                                  d_out_classes, d_out, d_stats);
 }
 
 int ndnet_ndt_prune(void* plan, void* stream, uint64_t num_desired, float* d_out, float* d_out_classes,
@@ -5223,8 +5277,8 @@ int ndnet_ndt_prune(void* plan, void* stream, uint64_t num_desired, float* d_out
   return NDNET_OK;
 }
 
-int ndnet_ndt_point_rows(void* plan, void* stream, const float* d_points, const float* d_rows_block,
-                         uint64_t num_desired, int fill, int32_t* d_point_rows) {
+int ndnet_ndt_point_rows_counts(void* plan, void* stream, const float* d_points, const float* d_rows_block,
+                                uint64_t num_desired, int fill, int32_t* d_point_rows, const int32_t* d_counts) {
   Plan* P = (Plan*)plan;
   if (!P || !d_points || !d_point_rows || num_desired == 0 || num_desired > P->k) return NDNET_ERR_ARG;
   if (fill != NDNET_POINT_FILL_NONE && fill != NDNET_POINT_FILL_NEAREST) return NDNET_ERR_ARG;
@@ -5232,9 +5286,14 @@ int ndnet_ndt_point_rows(void* plan, void* stream, const float* d_points, const 
   if (P->in_f64) return NDNET_ERR_ARG;  // float32 input only
   const dim3 grid((uint32_t)((P->n + kPrPts - 1) / kPrPts), (uint32_t)P->B);
   k_point_rows<<<grid, kPrThreads, pr_lds_bytes(P->ndcap, fill), (hipStream_t)stream>>>(
-      d_points, P->ctl, P->vox, P->alive, d_rows_block, d_point_rows, P->n, P->ndcap, num_desired, fill);
+      d_points, P->ctl, P->vox, P->alive, d_rows_block, d_point_rows, P->n, P->ndcap, num_desired, fill, d_counts);
   HIPCHK(hipGetLastError());
   return NDNET_OK;
+}
+
+int ndnet_ndt_point_rows(void* plan, void* stream, const float* d_points, const float* d_rows_block,
+                         uint64_t num_desired, int fill, int32_t* d_point_rows) {
+  return ndnet_ndt_point_rows_counts(plan, stream, d_points, d_rows_block, num_desired, fill, d_point_rows, nullptr);
 }
 
 // Stage dumps for the parity tests (host copies of one cloud's intermediates).

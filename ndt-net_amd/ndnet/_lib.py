@@ -88,6 +88,10 @@ EXPORTS = {
     "ndnet_ndt_run_f64": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_prune": (_I, [_P, _P, _U64, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_point_rows": (_I, [_P, _P, _P, _P, _U64, _I, _P]),
+    # ragged batches: the same with a device array of per-cloud point counts (NULL: the calls above)
+    "ndnet_ndt_run_counts": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "ndnet_ndt_run_f64_counts": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ndnet_ndt_point_rows_counts": (_I, [_P, _P, _P, _P, _U64, _I, _P, _P]),
     # include/ndnet_segment.h
     "ndnet_seg_point_labels": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_int32, _P, _P, _P]),
     "ndnet_seg_confusion": (_I, [_P, _P, _U64, _I, _P, _P]),

@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 
 from . import _lib, segment
-from .preprocessing.ndtnet_preprocessing import NdtPlan, ndt_multiscale, ndt_preprocessing, get_plan
+from .preprocessing.ndtnet_preprocessing import NdtPlan, check_counts, ndt_multiscale, ndt_preprocessing, get_plan
 
 
 # CU share of the pipelined NDT stage (ndnet_ndt_set_cu_share): k_front and
@@ -136,10 +136,22 @@ class GraphedSegmentation:
             ``self.point_labels`` are then the static ``[B, N]`` int32 buffers,
             overwritten by each replay.  For an ``NDTNetSegmentation`` without
             ``levels`` only (``ValueError`` otherwise).
+        ragged: ``True`` captures the step with a static int32 ``[batch]``
+            buffer ``self.counts`` (initialised to ``num_points``): cloud ``b``
+            of a replay is the first ``counts[b]`` points of ``points[b]``, as
+            ``ndt_preprocessing(..., counts=)`` defines it, so one graph serves
+            scans of any lengths up to ``num_points`` -- with ``levels`` and
+            with ``point_labels`` too (padding points get row and label -1).
+            The kernels read the counts on the device at replay.
 
     ``points`` is the static float32 input buffer; ``__call__(new_points)``
     copies into it, replays, and returns the static ``[B, num_nds, C+1]``
     output buffer (overwritten by the next replay -- clone to keep it).
+    With ``ragged``, ``__call__(new_points, counts)`` copies both in;
+    ``new_points`` may then be ``[B, m, 3]`` with ``m <= num_points``: it goes
+    to the leading part of the buffer and the rest -- padding for every count
+    up to ``m`` -- is left as it is.  Counts given as a CPU tensor or a
+    sequence are range-checked (``ValueError``); a device tensor is not.
 
     The graph keeps the precision mode it was captured with
     (``model.precision`` or ``pointnet_hip.PRECISION`` at construction): the
@@ -150,8 +162,10 @@ class GraphedSegmentation:
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,
                  device: Optional[torch.device] = None, warmup: int = 2, levels=None,
-                 point_labels: Optional[str] = None) -> None:
-        if point_labels is not None:  # (checked before any GPU work)
+                 point_labels: Optional[str] = None, ragged: bool = False) -> None:
+        if not isinstance(ragged, bool):  # (checked before any GPU work)
+            raise ValueError(f"ragged must be True or False, got {ragged!r}")
+        if point_labels is not None:
             from .models.ndtnet import NDTNetSegmentation
             if point_labels not in _lib.POINT_FILL:
                 raise ValueError(f"point_labels must be None, 'none' or 'nearest', got {point_labels!r}")
@@ -170,6 +184,8 @@ class GraphedSegmentation:
             num_nds = self.levels[0]
         self.model, self.num_nds, self.device = model, int(num_nds), dev
         self.points = torch.zeros((batch, num_points, 3), dtype=torch.float32, device=dev)
+        self.ragged = ragged
+        self.counts = torch.full((batch,), num_points, dtype=torch.int32, device=dev) if ragged else None
         self.fill = point_labels
         self.point_rows = self.point_labels = self._nd_labels = None
         if point_labels is not None:
@@ -191,12 +207,12 @@ class GraphedSegmentation:
 
     def _step(self):
         if self.levels:
-            return [self.model(p, c) for p, c, _ in ndt_multiscale(self.levels, self.points)]
-        p, c, _ = ndt_preprocessing(self.num_nds, self.points)
+            return [self.model(p, c) for p, c, _ in ndt_multiscale(self.levels, self.points, counts=self.counts)]
+        p, c, _ = ndt_preprocessing(self.num_nds, self.points, counts=self.counts)
         out = self.model(p, c)
         if self.fill is not None:
             rows = segment.point_rows(self.points, self.fill, ndt_preprocessing.last_plan,
-                                      ndt_preprocessing.last_rows, out=self.point_rows)
+                                      ndt_preprocessing.last_rows, out=self.point_rows, counts=self.counts)
             segment.point_labels(out, rows, out=self.point_labels, nd_labels=self._nd_labels)
         return out
 
@@ -205,9 +221,18 @@ class GraphedSegmentation:
         self.graph.replay()
         return self.out
 
-    def __call__(self, points: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, points: Optional[torch.Tensor] = None, counts=None) -> torch.Tensor:
+        if counts is not None:
+            if not self.ragged:
+                raise ValueError("counts need a graph built with ragged=True")
+            check_counts(counts, self.points.shape[0], self.points.shape[1])
         if points is not None:
-            self.points.copy_(points, non_blocking=True)
+            if self.ragged and points.dim() == 3 and points.shape[1] < self.points.shape[1]:
+                self.points[:, :points.shape[1]].copy_(points, non_blocking=True)
+            else:
+                self.points.copy_(points, non_blocking=True)
+        if counts is not None:
+            self.counts.copy_(torch.as_tensor(counts).to(torch.int32), non_blocking=True)
         return self.replay()
 
     def stats(self) -> list:

@@ -1,8 +1,10 @@
 """Farthest point sampling on the GPU: fixed-size batches from ragged scans.
 
-Every consumer here (``ndt_preprocessing``, ``Trainer.step``,
-``segment.segment_points``) takes ``[B, n, 3]`` with one ``n`` for all clouds;
-real scans have their own lengths.  ``farthest_point_sample`` picks
+``Trainer.step`` and ``PipelinedSegmentation`` take ``[B, n, 3]`` with one
+``n`` for all clouds; real scans have their own lengths.  (The NDT path --
+``ndt_preprocessing``, ``segment.segment_points``, ``GraphedSegmentation`` --
+also takes a padded batch with per-cloud ``counts`` and needs no cut.)
+``farthest_point_sample`` picks
 ``n_samples`` evenly spread points of every cloud in one HIP kernel
 (``ndnet_fps_run``, include/ndnet_fps.h: one workgroup per cloud, no launch
 and no host round trip inside the selection), ``fps_downsample`` gathers the

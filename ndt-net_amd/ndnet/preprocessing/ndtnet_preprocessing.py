@@ -18,6 +18,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _lib
+from .fps import _per_cloud
 
 
 class NdtPlan:
@@ -46,19 +47,35 @@ class NdtPlan:
                 pass
             self.handle = None
 
+    def _counts_ptr(self, counts: Optional[torch.Tensor]):
+        if counts is None:
+            return None
+        assert counts.is_contiguous() and counts.dtype == torch.int32 and counts.device == self.device
+        assert counts.shape == (self.batch,)
+        return counts.data_ptr()
+
     def run(self, points: torch.Tensor, labels: Optional[torch.Tensor], out: torch.Tensor,
-            out_classes: Optional[torch.Tensor], part: int = 0) -> None:
+            out_classes: Optional[torch.Tensor], part: int = 0, counts: Optional[torch.Tensor] = None) -> None:
         """part: 0 the whole run; 1 the front only (k_front); 2 the rest, after a
         part-1 call with the same arguments in stream order
-        (include/ndnet_amd.h ndnet_ndt_set_run_part)."""
+        (include/ndnet_amd.h ndnet_ndt_set_run_part).
+
+        counts: int32 ``[B]`` on the plan's device, or None.  Cloud ``b`` is
+        then its first ``counts[b]`` points alone -- ``points`` is the padded
+        ``[B, num_points, 3]`` batch, whose padding may hold anything -- and its
+        rows are those of that cloud run on its own.  A count outside
+        ``1 .. num_points`` fails its cloud (stats rc -20, zero rows).  The
+        kernels read the counts on the device: a captured run follows whatever
+        the buffer holds at replay (include/ndnet_amd.h ndnet_ndt_run_counts)."""
         assert points.is_contiguous() and points.dtype == torch.float32 and points.device == self.device
         assert out.is_contiguous() and out.shape == (self.batch, self.num_nds, 12)
         self.raise_sync_failures()
         st = _lib.stream_ptr(self.device)
         _lib.check(_lib.lib().ndnet_ndt_set_run_part(self.handle, int(part)), "ndnet_ndt_set_run_part")
-        rc = _lib.lib().ndnet_ndt_run(
+        rc = _lib.lib().ndnet_ndt_run_counts(
             self.handle, st, points.data_ptr(),
             labels.data_ptr() if labels is not None else None,
+            self._counts_ptr(counts),
             out.data_ptr(),
             out_classes.data_ptr() if out_classes is not None else None,
             self.stats.data_ptr())
@@ -154,14 +171,16 @@ class NdtPlan:
 
     def point_rows(self, points: torch.Tensor, rows_block: Optional[torch.Tensor] = None,
                    num_nds: Optional[int] = None, fill: str = "none",
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The output row of every input point, int32 ``[B, N]``, after the last
         ``run`` / ``prune`` of this plan on the same ``points`` (stream
         ordered; include/ndnet_amd.h ndnet_ndt_point_rows).  A point that
         contributed to no surviving row gets -1 (``fill="none"``) or the row
         whose mean is nearest (``fill="nearest"``: ``rows_block`` is the
         ``[B, num_nds, 12]`` block that level wrote).  ``num_nds``: the NDs of
-        the level last run (default: the plan's)."""
+        the level last run (default: the plan's).  ``counts``: the int32
+        ``[B]`` device tensor of the run it follows (None for a fixed-size
+        run); a padding point (``i >= counts[b]``) gets -1 under both fills."""
         assert points.is_contiguous() and points.dtype == torch.float32 and points.device == self.device
         assert points.shape == (self.batch, self.num_points, 3)
         if fill not in _lib.POINT_FILL:
@@ -176,9 +195,9 @@ class NdtPlan:
             out = torch.empty((self.batch, self.num_points), dtype=torch.int32, device=self.device)
         assert out.is_contiguous() and out.dtype == torch.int32 and out.device == self.device
         assert out.shape == (self.batch, self.num_points)
-        rc = _lib.lib().ndnet_ndt_point_rows(self.handle, _lib.stream_ptr(self.device), points.data_ptr(),
-                                             rows_block.data_ptr() if rows_block is not None else None, k,
-                                             _lib.POINT_FILL[fill], out.data_ptr())
+        rc = _lib.lib().ndnet_ndt_point_rows_counts(self.handle, _lib.stream_ptr(self.device), points.data_ptr(),
+                                                    rows_block.data_ptr() if rows_block is not None else None, k,
+                                                    _lib.POINT_FILL[fill], out.data_ptr(), self._counts_ptr(counts))
         _lib.check(rc, "ndnet_ndt_point_rows")
         return out
 
@@ -226,8 +245,23 @@ def check_stats(plan: "NdtPlan") -> None:
         raise NdtCloudError(rcs)
 
 
+def check_counts(counts, batch: int, num_points: int) -> None:
+    """The host's check of per-cloud point counts: shape ``[batch]`` and, when
+    they arrive as a CPU tensor or a sequence, every value in
+    ``1 .. num_points`` (``ValueError``).  A device tensor's values are not
+    read -- that would synchronise; the kernels fail such a cloud with rc -20."""
+    if counts is None:
+        return
+    on_device = isinstance(counts, torch.Tensor) and counts.is_cuda
+    t = counts if on_device else torch.as_tensor(counts)
+    if tuple(t.shape) != (batch,):
+        raise ValueError(f"counts must have shape ({batch},), got {tuple(t.shape)}")
+    if not on_device and (int(t.min()) < 1 or int(t.max()) > num_points):
+        raise ValueError(f"every count must lie in 1 .. n = {num_points}, got {int(t.min())} .. {int(t.max())}")
+
+
 def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor = None,
-                      num_classes: int = None, *, check: Optional[bool] = None
+                      num_classes: int = None, *, counts=None, check: Optional[bool] = None
                       ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Downsample a batch of clouds to ``num_nds`` normal distributions.
 
@@ -236,6 +270,15 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
         points: ``[B, N, 3]`` float tensor (any device; computed on the GPU).
         classes: optional ``[B, N, num_classes + 1]`` one-hot labels.
         num_classes: number of classes (labels take ``num_classes + 1`` values).
+        counts: optional ``[B]`` tensor or sequence (converted to int32 on the
+            device) for a ragged batch: ``points`` is then padded to
+            ``[B, n_max, 3]`` (``collate_padded``), cloud ``b`` consists of its
+            first ``counts[b]`` points, and its rows are, bit for bit, those
+            of that cloud run alone; the padding (points and classes) may
+            hold anything.  Counts given as a CPU tensor or a sequence are
+            range-checked here (``ValueError`` outside ``1 .. N``); a device
+            tensor is not read on the host -- a bad count fails its cloud
+            with rc -20 and zero rows.
 
     Returns:
         ``(points [B, num_nds, 3], covariances [B, num_nds, 9], classes one-hot
@@ -256,6 +299,10 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
     a flag in host memory and the plan's next call raises ``NdtCloudError``
     whatever ``check`` is (``NdtPlan.raise_sync_failures``).
     """
+    if counts is not None:  # (before any GPU work)
+        if points.dim() != 3 or points.shape[2] != 3:
+            raise ValueError(f"points must be [B, N, 3], got {tuple(points.shape)}")
+        check_counts(counts, points.shape[0], points.shape[1])
     _lib.require_gpu()
     src_device = points.device
     dev = src_device if src_device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
@@ -263,6 +310,7 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
     B, N, D = pts.shape
     if D != 3:
         raise ValueError(f"points must be [B, N, 3], got {tuple(pts.shape)}")
+    counts = _per_cloud(counts, B, dev, "counts")
     labelled = classes is not None
     if labelled and num_classes is None:
         raise ValueError("num_classes is required with classes")
@@ -283,9 +331,10 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
         else:
             labels = torch.argmax(oh, dim=2).to(torch.int32).contiguous()
         out_cls = torch.empty((B, num_nds, ncls + 1), dtype=torch.float32, device=dev)
-    plan.run(pts, labels, out, out_cls)
+    plan.run(pts, labels, out, out_cls, counts=counts)
     ndt_preprocessing.last_plan = plan
     ndt_preprocessing.last_rows = out  # the device block (ndnet.segment.point_rows reads it)
+    ndt_preprocessing.last_counts = counts  # ... and the run's counts on the device, or None
     if (CHECK_RC if check is None else check) and not torch.cuda.is_current_stream_capturing():
         check_stats(plan)
     if src_device != dev:
@@ -296,20 +345,24 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
 
 ndt_preprocessing.last_plan = None
 ndt_preprocessing.last_rows = None
+ndt_preprocessing.last_counts = None
 
 
-def ndt_multiscale(levels, points: torch.Tensor, classes: torch.Tensor = None, num_classes: int = None) -> list:
+def ndt_multiscale(levels, points: torch.Tensor, classes: torch.Tensor = None, num_classes: int = None, *,
+                   counts=None) -> list:
     """Multi-level NDT of a batch (config C5, tools/train_multiscale.py's
     levels): ``downsample(levels[0])`` then ``prune(levels[i])`` for each
     further, smaller level on the retained KL list -- NDT_Sampler.downsample /
     .prune (ndt_legacy.py:111-240) for every cloud at once, all on the GPU.
 
     Returns one ``(points [B,k,3], covariances [B,k,9], classes or None)`` per
-    level, as ndt_preprocessing does for one level."""
+    level, as ndt_preprocessing does for one level.  ``counts``: per-cloud
+    point counts of a ragged batch, as ndt_preprocessing takes them (the prune
+    levels read the plan's state only)."""
     levels = [int(k) for k in levels]
     if not levels or any(b >= a for a, b in zip(levels, levels[1:])):
         raise ValueError(f"levels must be strictly decreasing, got {levels}")
-    p, c, cls = ndt_preprocessing(levels[0], points, classes, num_classes)
+    p, c, cls = ndt_preprocessing(levels[0], points, classes, num_classes, counts=counts)
     out = [(p, c, cls)]
     plan = ndt_preprocessing.last_plan
     dev = plan.device

@@ -19,17 +19,23 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .preprocessing.ndtnet_preprocessing import NdtPlan, ndt_preprocessing
+from .preprocessing.fps import _per_cloud
+from .preprocessing.ndtnet_preprocessing import NdtPlan, check_counts, ndt_preprocessing
 
 
 def point_rows(points: torch.Tensor, fill: str = "none", plan: Optional[NdtPlan] = None,
-               rows_block: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               rows_block: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               counts=None) -> torch.Tensor:
     """The output row of every point of ``points`` ``[B, N, 3]``, int32
     ``[B, N]``: -1 (``fill="none"``) or the nearest row (``fill="nearest"``)
     for a point that contributed to no surviving ND.  ``plan`` defaults to the
     plan of the last ``ndt_preprocessing`` / ``ndt_multiscale`` call and
     ``rows_block`` to the ``[B, k, 12]`` block it returned (its last level's);
-    ``points`` must be the points that call ran on."""
+    ``points`` must be the points that call ran on.  ``counts``: the per-cloud
+    point counts that run took (a ``[B]`` tensor or sequence; with the
+    defaulted plan, the last call's); padding points get -1."""
+    if counts is not None and points.dim() == 3:
+        check_counts(counts, points.shape[0], points.shape[1])
     _lib.require_gpu()
     if plan is None:
         plan = ndt_preprocessing.last_plan
@@ -37,9 +43,12 @@ def point_rows(points: torch.Tensor, fill: str = "none", plan: Optional[NdtPlan]
             raise RuntimeError("point_rows needs a plan: call ndt_preprocessing first")
         if rows_block is None:
             rows_block = ndt_preprocessing.last_rows
+        if counts is None:
+            counts = ndt_preprocessing.last_counts
     pts = points.to(device=plan.device, dtype=torch.float32).contiguous()
     k = rows_block.shape[1] if rows_block is not None else None
-    return plan.point_rows(pts, rows_block, k, fill, out)
+    counts = _per_cloud(counts, pts.shape[0], plan.device, "counts")
+    return plan.point_rows(pts, rows_block, k, fill, out, counts=counts)
 
 
 def point_labels(scores: torch.Tensor, rows: torch.Tensor, unassigned: int = -1,
@@ -68,7 +77,7 @@ def point_labels(scores: torch.Tensor, rows: torch.Tensor, unassigned: int = -1,
     return out
 
 
-def segment_points(model, num_nds: int, points: torch.Tensor, fill: str = "nearest"
+def segment_points(model, num_nds: int, points: torch.Tensor, fill: str = "nearest", counts=None
                    ) -> Tuple[torch.Tensor, torch.Tensor]:
     """A class for every point of ``points`` ``[B, N, 3]``: ``ndt_preprocessing``,
     ``model`` (an eval-mode ``NDTNetSegmentation``), the points' rows and the
@@ -78,12 +87,17 @@ def segment_points(model, num_nds: int, points: torch.Tensor, fill: str = "neare
     ``fill="nearest"`` (default) a point that fell into a pruned ND or the
     ``N % 8`` tail takes the class of the nearest surviving ND; with
     ``fill="none"`` it gets -1.  Every point of a cloud whose NDT failed gets
-    -1 either way."""
+    -1 either way.
+
+    ``counts`` (a ``[B]`` tensor or sequence): a ragged batch, ``points``
+    padded to ``[B, n_max, 3]`` (``collate_padded``); cloud ``b`` is its first
+    ``counts[b]`` points, labelled as when it is run alone, and the padding
+    points get -1 (``confusion`` leaves them out)."""
     with torch.no_grad():
-        p, c, _ = ndt_preprocessing(int(num_nds), points)
+        p, c, _ = ndt_preprocessing(int(num_nds), points, counts=counts)
         plan, block = ndt_preprocessing.last_plan, ndt_preprocessing.last_rows
         log_probs = model(p.to(plan.device), c.to(plan.device))
-        rows = point_rows(points, fill, plan, block)
+        rows = point_rows(points, fill, plan, block, counts=ndt_preprocessing.last_counts)
         return point_labels(log_probs, rows), log_probs
 
 
