@@ -38,6 +38,17 @@ int ndnet_seg_point_labels(const float *d_scores, const int32_t *d_point_rows, i
 int ndnet_seg_confusion(const int32_t *d_pred, const int32_t *d_gt, uint64_t count, int cols,
                         unsigned long long *d_conf, void *stream);
 
+/* The class histogram of every ND row, the target of the point-level training loss
+ * (ndnet_tr_nll_hist, ndnet_train.h): d_hist[b][r][c] = the number of points i of cloud b with
+ * d_point_rows[b][i] == r and d_point_labels[b][i] == c.  A point is skipped when its row lies
+ * outside 0..k-1, its label outside 0..cols-1, or its label equals ignore_label (-1: none).
+ * d_point_rows and d_point_labels [B][n] int32, d_hist [B][k][cols] int32.  The call clears d_hist
+ * itself, in stream order, then adds one 32-bit global atomic per counted point: integer counts,
+ * so the table is the same bits whatever the order.
+ * NDNET_ERR_ARG for a NULL pointer or B, n, k or cols < 1. */
+int ndnet_seg_row_hist(const int32_t *d_point_rows, const int32_t *d_point_labels, int B, uint64_t n, uint64_t k,
+                       int cols, int32_t ignore_label, int32_t *d_hist, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,31 @@ int ndnet_tr_nll_onehot(const float *logp, const float *gt, double *part, float 
                         void *stream);
 int ndnet_tr_nll_onehot_bwd(const float *gt, const float *dloss, float *dlogp, int B, int C, int N, void *stream);
 
+/* The point-level loss: the mean NLL of every labelled point under the
+ * prediction of the ND row it was folded into.  hist [B][N][C] int32 (counts
+ * >= 0, ndnet_seg_row_hist of ndnet_segment.h: hist[b][n][c] points of class c
+ * in row n) takes the place of the one-hot gt; logp, pred and dlogp are
+ * [B][C][N] as above, C <= 32.
+ *   loss = -sum_{b,n,c} hist[b][n][c] logp[b][c][n] / W,  W = sum hist
+ * Every term and the sum are taken in double in a fixed order (part: (B N +
+ * 63) / 64 doubles of scratch); a term with a zero count is skipped, so
+ * 0 * -inf adds 0; W is summed as an exact 64-bit integer into wsum[0] (the
+ * call clears it in stream order) and kept there for the backward; W == 0
+ * gives loss 0.
+ *   dlogp[b][c][n] = -hist[b][n][c] dloss / W, all zeros when W == 0.
+ * ndnet_tr_hist_match_cm: ctr[0] += sum_{b,n} hist[b][n][first argmax_c
+ * pred[b][c][n]] (NaN counting as a maximum) -- the points whose row predicts
+ * their class -- and ctr[1] += W, both 64-bit; ctr[2] counts workgroups, and
+ * the last writes acc[0] = float(ctr[0]) / float(ctr[1]), 0 when W == 0 (acc
+ * may be NULL).  The caller zeroes ctr[0..2].
+ * NDNET_ERR_ARG for a NULL pointer, a dimension < 1 or C > 32. */
+int ndnet_tr_nll_hist(const float *logp, const int32_t *hist, double *part, int64_t *wsum, float *loss, int B, int C,
+                      int N, void *stream);
+int ndnet_tr_nll_hist_bwd(const int32_t *hist, const int64_t *wsum, const float *dloss, float *dlogp, int B, int C,
+                          int N, void *stream);
+int ndnet_tr_hist_match_cm(const float *pred, const int32_t *hist, int B, int C, int N, uint64_t *ctr, float *acc,
+                           void *stream);
+
 /* The point transform t1 of the train forward (ndtnet.py:141-147, t . p and
  * t . C with the covariance multiplied on the left only): t [B][3][3], pts
  * [B][N][pld] (p in columns 0-2), extra [B][N][eld] (C row-major in columns

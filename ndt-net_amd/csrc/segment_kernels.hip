@@ -10,6 +10,9 @@
 //   k_seg_confusion     grid-stride over the points; a per-workgroup LDS
 //                       histogram flushed with 64-bit global atomics, or one
 //                       64-bit global atomic per point for wide matrices
+//   k_seg_row_hist      a thread per point: the class histogram of every ND row
+//                       (the point-level training loss), one return-less
+//                       32-bit global atomic per counted point
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -120,6 +123,23 @@ __global__ void __launch_bounds__(kSegThreads) k_seg_confusion(const int32_t* __
   }
 }
 
+// hist[b][row][label] += 1 for every point of cloud b (grid y) with a row in
+// 0..k-1 and a label in 0..cols-1 other than `ignore`: a thread per point, two
+// coalesced int32 loads and one return-less 32-bit global atomic.  Integer
+// counts: any arrival order gives the same table.
+__global__ void __launch_bounds__(kSegThreads) k_seg_row_hist(const int32_t* __restrict__ point_rows,
+                                                            const int32_t* __restrict__ point_labels, uint64_t n,
+                                                            uint64_t k, int cols, int32_t ignore,
+                                                            int32_t* __restrict__ hist) {
+  const uint64_t i = (uint64_t)blockIdx.x * kSegThreads + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t b = blockIdx.y;
+  const int32_t row = point_rows[b * n + i], lb = point_labels[b * n + i];
+  if (row < 0 || (uint64_t)row >= k || lb < 0 || lb >= cols || lb == ignore) return;
+  int32_t* cell = hist + (b * k + (uint64_t)row) * (uint64_t)cols + (uint64_t)lb;
+  (void)__hip_atomic_fetch_add(cell, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace
 
 extern "C" {
@@ -148,6 +168,21 @@ int ndnet_seg_confusion(const int32_t* d_pred, const int32_t* d_gt, uint64_t cou
   hipStream_t st = (hipStream_t)stream;
   if (cols <= kConfLdsCols) k_seg_confusion<true><<<(uint32_t)blocks, kSegThreads, 0, st>>>(d_pred, d_gt, count, cols, d_conf);
   else k_seg_confusion<false><<<(uint32_t)blocks, kSegThreads, 0, st>>>(d_pred, d_gt, count, cols, d_conf);
+  SEG_HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_seg_row_hist(const int32_t* d_point_rows, const int32_t* d_point_labels, int B, uint64_t n, uint64_t k,
+                       int cols, int32_t ignore_label, int32_t* d_hist, void* stream) {
+  if (!d_point_rows || !d_point_labels || !d_hist || B < 1 || n < 1 || k < 1 || cols < 1) return NDNET_ERR_ARG;
+  const uint64_t pblocks = (n + kSegThreads - 1) / kSegThreads;
+  // (rows are int32, so k above 2^31 holds no more of them; the table's bytes stay in 64 bits)
+  if (pblocks > 0x7fffffffull || B > 65535 || k > 0x80000000ull) return NDNET_ERR_ARG;
+  if ((uint64_t)B * k > (1ull << 60) / (uint64_t)cols) return NDNET_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  SEG_HIPCHK(hipMemsetAsync(d_hist, 0, (uint64_t)B * k * (uint64_t)cols * sizeof(int32_t), st));
+  k_seg_row_hist<<<dim3((uint32_t)pblocks, (uint32_t)B), kSegThreads, 0, st>>>(d_point_rows, d_point_labels, n, k, cols,
+                                                                              ignore_label, d_hist);
   SEG_HIPCHK(hipGetLastError());
   return NDNET_OK;
 }

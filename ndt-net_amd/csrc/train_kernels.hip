@@ -1294,6 +1294,145 @@ __global__ __launch_bounds__(kLsmT) void k_tr_argmax_match_cm(const float* __res
   }
 }
 
+// ---- the point-level loss: the NLL of every point under the prediction of
+// the ND row it was folded into, through the rows' class histograms
+// (ndnet_seg_row_hist: hist [B][N][C] int32 in the place of the one-hot gt)
+// ----
+
+// the workgroup's histogram rows [t0, t0 + kLsmT) x C staged in LDS, as
+// nll_stage_gt stages the one-hot rows
+__device__ inline const int32_t* nll_stage_hist(int32_t* s_h, const int32_t* __restrict__ hist, int64_t pts, int C) {
+  const int64_t t0 = (int64_t)blockIdx.x * kLsmT;
+  const int64_t n = (pts - t0 < kLsmT ? pts - t0 : kLsmT) * C;
+  const int32_t* src = hist + t0 * C;
+  for (int64_t i = threadIdx.x; i < n; i += kLsmT) s_h[i] = src[i];
+  __syncthreads();
+  return s_h + threadIdx.x * C;
+}
+
+// Per-workgroup partial of sum_{b,n,c} hist[b][n][c] * logp[b][c][n], each
+// term and the sums in double and in a fixed order (a count reaches 2^31: its
+// product with a log-prob is exact in double), a term with a zero count
+// skipped (0 * -inf adds nothing); the workgroup's share of W = sum hist goes
+// to wsum with one 64-bit integer atomic (exact, so order-free).
+__global__ __launch_bounds__(kLsmT) void k_tr_nll_hist_part(const float* __restrict__ logp,
+                                                            const int32_t* __restrict__ hist,
+                                                            double* __restrict__ part,
+                                                            unsigned long long* __restrict__ wsum, int Bn, int C,
+                                                            int N) {
+  __shared__ int32_t s_h[kLsmT * kLsmC];
+  const int64_t pts = (int64_t)Bn * N;
+  const int64_t t = (int64_t)blockIdx.x * kLsmT + threadIdx.x;
+  const int64_t tc = t < pts ? t : pts - 1;
+  const int64_t base = tc / N * C * N + tc % N;
+  float lp[kLsmC];
+#pragma unroll
+  for (int c = 0; c < kLsmC; c++) lp[c] = c < C ? logp[base + (int64_t)c * N] : 0.0f;
+  const int32_t* h = nll_stage_hist(s_h, hist, pts, C);
+  double v = 0.0;
+  unsigned long long w = 0;
+  if (t < pts) {
+#pragma unroll
+    for (int c = 0; c < kLsmC; c++)
+      if (c < C && h[c] != 0) {
+        v += (double)h[c] * (double)lp[c];
+        w += (unsigned long long)(long long)h[c];
+      }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    v += __shfl_xor(v, o);
+    w += __shfl_xor(w, o);
+  }
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = v;
+    if (w) __hip_atomic_fetch_add(wsum, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// loss = -(sum of the parts in order) / W, 0 when W == 0
+__global__ __launch_bounds__(64) void k_tr_nll_hist_sum(const double* __restrict__ part, int nparts,
+                                                        const unsigned long long* __restrict__ wsum,
+                                                        float* __restrict__ loss) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 64) s += part[i];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (threadIdx.x == 0) {
+    const long long W = (long long)wsum[0];
+    loss[0] = W != 0 ? (float)(-s / (double)W) : 0.0f;
+  }
+}
+
+// dlogp[b][c][n] = -hist[b][n][c] * dloss / W (the quotient in double, one
+// rounding to fp32 per element); all zeros when W == 0
+__global__ __launch_bounds__(kLsmT) void k_tr_nll_hist_bwd(const int32_t* __restrict__ hist,
+                                                           const unsigned long long* __restrict__ wsum,
+                                                           const float* __restrict__ dloss, float* __restrict__ dlogp,
+                                                           int Bn, int C, int N) {
+  __shared__ int32_t s_h[kLsmT * kLsmC];
+  const int64_t pts = (int64_t)Bn * N;
+  const int32_t* h = nll_stage_hist(s_h, hist, pts, C);
+  const int64_t t = (int64_t)blockIdx.x * kLsmT + threadIdx.x;
+  if (t >= pts) return;
+  const int64_t base = t / N * C * N + t % N;
+  const long long W = (long long)wsum[0];
+  const double s = W != 0 ? -(double)dloss[0] / (double)W : 0.0;
+#pragma unroll
+  for (int c = 0; c < kLsmC; c++)
+    if (c < C) dlogp[base + (int64_t)c * N] = h[c] != 0 ? (float)((double)h[c] * s) : 0.0f;
+}
+
+// The point-level accuracy: ctr[0] += sum over the rows of hist[row][first
+// argmax of pred's row] (the points the row's prediction gets right), ctr[1]
+// += W; pred channel-major as k_tr_argmax_match_cm reads it.  The last
+// workgroup (ticket ctr[2]) writes acc = float(ctr[0]) / float(ctr[1]), 0
+// when W == 0.  The caller zeroes ctr[0..2].
+__global__ __launch_bounds__(kLsmT) void k_tr_hist_match_cm(const float* __restrict__ pred,
+                                                            const int32_t* __restrict__ hist, int Bn, int C, int N,
+                                                            unsigned long long* __restrict__ ctr,
+                                                            float* __restrict__ acc) {
+  __shared__ int32_t s_h[kLsmT * kLsmC];
+  const int64_t pts = (int64_t)Bn * N;
+  const int64_t t = (int64_t)blockIdx.x * kLsmT + threadIdx.x;
+  const int64_t tc = t < pts ? t : pts - 1;
+  const int64_t base = tc / N * C * N + tc % N;
+  float v[kLsmC];
+#pragma unroll
+  for (int c = 0; c < kLsmC; c++) v[c] = c < C ? pred[base + (int64_t)c * N] : 0.0f;
+  const int32_t* h = nll_stage_hist(s_h, hist, pts, C);
+  int bi = 0;
+  float bv = v[0];
+  unsigned long long w = 0, m = 0;
+  if (t < pts) {
+    w = (unsigned long long)(long long)h[0];
+#pragma unroll
+    for (int c = 1; c < kLsmC; c++) {
+      if (c < C) {
+        if (!(bv != bv) && (v[c] > bv || v[c] != v[c])) {
+          bv = v[c];
+          bi = c;
+        }
+        w += (unsigned long long)(long long)h[c];
+      }
+    }
+    m = (unsigned long long)(long long)h[bi];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m += __shfl_xor(m, o);
+    w += __shfl_xor(w, o);
+  }
+  if (threadIdx.x == 0) {
+    if (m) __hip_atomic_fetch_add(&ctr[0], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (w) __hip_atomic_fetch_add(&ctr[1], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the counts have been added before the ticket
+    if (__hip_atomic_fetch_add(&ctr[2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 && acc) {
+      const unsigned long long M = __hip_atomic_load(&ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long W = __hip_atomic_load(&ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      acc[0] = W != 0 ? (float)M / (float)W : 0.0f;
+    }
+  }
+}
+
 // ---- the point transform t1 (reference ndtnet.py:141-147: t . p and
 // t . C, left product only) of the train forward ----
 //
@@ -1774,6 +1913,42 @@ extern "C" int ndnet_tr_nll_onehot_bwd(const float* gt, const float* dloss, floa
   if (C > kLsmC) return -20;  // the classes of a point are held in registers
   const int64_t pts = (int64_t)B * N;
   k_tr_nll_bwd<<<(unsigned)((pts + kLsmT - 1) / kLsmT), kLsmT, 0, (hipStream_t)stream>>>(gt, dloss, dlogp, B, C, N);
+  return launched();
+}
+
+extern "C" int ndnet_tr_nll_hist(const float* logp, const int32_t* hist, double* part, int64_t* wsum, float* loss, int B,
+                                 int C, int N, void* stream) {
+  if (!logp || !hist || !part || !wsum || !loss || B <= 0 || C <= 0 || N <= 0) return -20;
+  if (C > kLsmC) return -20;  // the classes of a point are held in registers
+  const int64_t pts = (int64_t)B * N;
+  if ((pts + kLsmT - 1) / kLsmT > (int64_t)INT32_MAX) return -20;
+  const unsigned blocks = (unsigned)((pts + kLsmT - 1) / kLsmT);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(wsum, 0, sizeof(int64_t), st) != hipSuccess) return -21;
+  unsigned long long* w = reinterpret_cast<unsigned long long*>(wsum);
+  k_tr_nll_hist_part<<<blocks, kLsmT, 0, st>>>(logp, hist, part, w, B, C, N);
+  k_tr_nll_hist_sum<<<1, 64, 0, st>>>(part, (int)blocks, w, loss);
+  return launched();
+}
+
+extern "C" int ndnet_tr_nll_hist_bwd(const int32_t* hist, const int64_t* wsum, const float* dloss, float* dlogp, int B,
+                                     int C, int N, void* stream) {
+  if (!hist || !wsum || !dloss || !dlogp || B <= 0 || C <= 0 || N <= 0) return -20;
+  if (C > kLsmC) return -20;  // the classes of a point are held in registers
+  const int64_t pts = (int64_t)B * N;
+  if ((pts + kLsmT - 1) / kLsmT > (int64_t)INT32_MAX) return -20;
+  k_tr_nll_hist_bwd<<<(unsigned)((pts + kLsmT - 1) / kLsmT), kLsmT, 0, (hipStream_t)stream>>>(
+      hist, reinterpret_cast<const unsigned long long*>(wsum), dloss, dlogp, B, C, N);
+  return launched();
+}
+
+extern "C" int ndnet_tr_hist_match_cm(const float* pred, const int32_t* hist, int B, int C, int N, uint64_t* ctr,
+                                      float* acc, void* stream) {
+  const int64_t rows = (int64_t)B * N;
+  if (!pred || !hist || !ctr || B <= 0 || C <= 0 || N <= 0 || C > kLsmC) return -20;
+  if ((rows + kLsmT - 1) / kLsmT > (int64_t)INT32_MAX) return -20;
+  k_tr_hist_match_cm<<<(unsigned)((rows + kLsmT - 1) / kLsmT), kLsmT, 0, (hipStream_t)stream>>>(
+      pred, hist, B, C, N, reinterpret_cast<unsigned long long*>(ctr), acc);
   return launched();
 }
 

@@ -95,6 +95,7 @@ EXPORTS = {
     # include/ndnet_segment.h
     "ndnet_seg_point_labels": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_int32, _P, _P, _P]),
     "ndnet_seg_confusion": (_I, [_P, _P, _U64, _I, _P, _P]),
+    "ndnet_seg_row_hist": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_int32, _P, _P]),
     # include/ndnet_fps.h
     "ndnet_fps_run": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
     "ndnet_fps_run_f64": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
@@ -178,6 +179,9 @@ TRAIN_EXPORTS: dict = {
     "ndnet_tr_log_softmax_c_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ndnet_tr_nll_onehot": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ndnet_tr_nll_onehot_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ndnet_tr_nll_hist": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ndnet_tr_nll_hist_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ndnet_tr_hist_match_cm": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "ndnet_tr_adam": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                            ctypes.c_double, _P]),
 }

@@ -669,3 +669,43 @@ def nll_onehot(logp: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
     logp [B,C,N] (the model's log-softmax before its transpose), gt [B,N,C]."""
     return _NllOneHot.apply(logp, gt)
 
+
+class _NllHist(torch.autograd.Function):
+    """-sum(hist * logp^T) / sum(hist) for logp [B,C,N] and the rows' class
+    histograms hist [B,N,C] int32 (zero counts skipped; 0 when hist is empty)."""
+
+    @staticmethod
+    def forward(ctx, logp, hist):
+        logp, hist = logp.contiguous(), hist.contiguous()
+        _check_f32(logp)
+        if hist.dtype != torch.int32 or hist.device != logp.device:
+            raise ValueError("the histogram is an int32 tensor on logp's device")
+        Bn, C, N = logp.shape
+        if hist.shape != (Bn, N, C):
+            raise ValueError(f"hist must be {(Bn, N, C)}, got {tuple(hist.shape)}")
+        part = torch.empty(-(-(Bn * N) // 64), device=logp.device, dtype=torch.float64)
+        wsum = torch.empty(1, device=logp.device, dtype=torch.int64)
+        loss = torch.empty((), device=logp.device, dtype=torch.float32)
+        _lib.check(_lib.lib().ndnet_tr_nll_hist(logp.data_ptr(), hist.data_ptr(), part.data_ptr(), wsum.data_ptr(),
+                                                loss.data_ptr(), Bn, C, N, _stream()), "ndnet_tr_nll_hist")
+        ctx.save_for_backward(hist, wsum)
+        ctx.shape = logp.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        hist, wsum = ctx.saved_tensors
+        Bn, C, N = ctx.shape
+        dl = dloss.contiguous().float().reshape(1)
+        dlogp = torch.empty(Bn, C, N, device=hist.device, dtype=torch.float32)
+        _lib.check(_lib.lib().ndnet_tr_nll_hist_bwd(hist.data_ptr(), wsum.data_ptr(), dl.data_ptr(), dlogp.data_ptr(),
+                                                    Bn, C, N, _stream()), "ndnet_tr_nll_hist_bwd")
+        return dlogp, None
+
+
+def nll_hist(logp: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
+    """The point-level training loss (ndnet.training.point_loss) on the HIP
+    kernels: logp [B,C,N] (the model's log-softmax before its transpose), hist
+    [B,N,C] int32 (ndnet.segment.row_histogram)."""
+    return _NllHist.apply(logp, hist)
+

@@ -260,6 +260,36 @@ def check_counts(counts, batch: int, num_points: int) -> None:
         raise ValueError(f"every count must lie in 1 .. n = {num_points}, got {int(t.min())} .. {int(t.max())}")
 
 
+def check_class_ids(classes: Optional[torch.Tensor], points: torch.Tensor) -> None:
+    """The host's check of labels given as class ids: a 2-D ``classes`` must be
+    an integer tensor of shape ``points.shape[:2]`` (``ValueError``).  One-hot
+    labels (3-D) and ``None`` pass."""
+    if classes is None or classes.dim() != 2:
+        return
+    if classes.is_floating_point() or classes.is_complex() or classes.dtype == torch.bool:
+        raise ValueError(f"classes [B, N] must hold integer class ids, got {classes.dtype} "
+                         "(one-hot labels are [B, N, num_classes + 1])")
+    if tuple(classes.shape) != tuple(points.shape[:2]):
+        raise ValueError(f"integer classes must have shape {tuple(points.shape[:2])}, got {tuple(classes.shape)}")
+
+
+def class_ids(classes: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    """The plan's int32 ``[B, N]`` labels on ``dev``: integer class ids
+    ``[B, N]`` as they come, or the first-max argmax of one-hot labels
+    ``[B, N, num_classes + 1]``, as ndtnet_preprocessing.py:34 does per cloud."""
+    oh = classes.to(dev)
+    if oh.dim() == 2:
+        return oh.to(torch.int32).contiguous()
+    if oh.dtype == torch.float32:  # one HIP pass (torch's argmax + int cast: ~160 us at 16 x 100k x 29)
+        oh = oh.contiguous()
+        labels = torch.empty(oh.shape[:2], dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().ndnet_row_argmax(oh.data_ptr(), oh.shape[0] * oh.shape[1], oh.shape[2],
+                                               labels.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                   "ndnet_row_argmax")
+        return labels
+    return torch.argmax(oh, dim=2).to(torch.int32).contiguous()
+
+
 def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor = None,
                       num_classes: int = None, *, counts=None, check: Optional[bool] = None
                       ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
@@ -268,7 +298,13 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
     Args:
         num_nds: NDs per cloud (the reference's ``n_desired_nds``).
         points: ``[B, N, 3]`` float tensor (any device; computed on the GPU).
-        classes: optional ``[B, N, num_classes + 1]`` one-hot labels.
+        classes: optional ``[B, N, num_classes + 1]`` one-hot labels, or an
+            integer tensor ``[B, N]`` of class ids (``CARLA_Seg`` /
+            ``collate_padded`` deliver these): the ids go to the plan as its
+            int32 labels, with no one-hot and no argmax pass.  An id outside
+            ``0 .. num_classes`` is left out of its voxel's histogram.  A
+            floating-point ``[B, N]`` tensor or another shape is a
+            ``ValueError``.
         num_classes: number of classes (labels take ``num_classes + 1`` values).
         counts: optional ``[B]`` tensor or sequence (converted to int32 on the
             device) for a ragged batch: ``points`` is then padded to
@@ -303,6 +339,7 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
         if points.dim() != 3 or points.shape[2] != 3:
             raise ValueError(f"points must be [B, N, 3], got {tuple(points.shape)}")
         check_counts(counts, points.shape[0], points.shape[1])
+    check_class_ids(classes, points)
     _lib.require_gpu()
     src_device = points.device
     dev = src_device if src_device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
@@ -320,16 +357,7 @@ def ndt_preprocessing(num_nds: int, points: torch.Tensor, classes: torch.Tensor 
     out_cls = None
     labels = None
     if labelled:
-        # argmax of the one-hot labels, as ndtnet_preprocessing.py:34 does per cloud
-        oh = classes.to(dev)
-        if oh.dtype == torch.float32:  # one HIP pass (torch's argmax + int cast: ~160 us at 16 x 100k x 29)
-            oh = oh.contiguous()
-            labels = torch.empty(oh.shape[:2], dtype=torch.int32, device=dev)
-            _lib.check(_lib.lib().ndnet_row_argmax(oh.data_ptr(), oh.shape[0] * oh.shape[1], oh.shape[2],
-                                                   labels.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "ndnet_row_argmax")
-        else:
-            labels = torch.argmax(oh, dim=2).to(torch.int32).contiguous()
+        labels = class_ids(classes, dev)
         out_cls = torch.empty((B, num_nds, ncls + 1), dtype=torch.float32, device=dev)
     plan.run(pts, labels, out, out_cls, counts=counts)
     ndt_preprocessing.last_plan = plan

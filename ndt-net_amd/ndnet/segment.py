@@ -11,6 +11,10 @@ plain torch.
     labels, log_probs = segment_points(model, 1000, points)       # [B, N] int32
     conf = confusion(labels, gt, model.num_classes)               # [C + 1, C + 1]
     per_class, mean = iou(conf)
+
+``row_histogram`` goes the other way for training: the points' rows and labels
+give every ND row its class histogram, the target of the point-level loss
+(``ndnet.training.point_loss``).
 """
 from __future__ import annotations
 
@@ -115,6 +119,30 @@ def confusion(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch.T
                                         _lib.stream_ptr(pred.device))
     _lib.check(rc, "ndnet_seg_confusion")
     return conf[:-1].view(cols, cols)
+
+
+def row_histogram(rows: torch.Tensor, labels: torch.Tensor, num_nds: int, cols: int, ignore_label: int = -1,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The class histogram of every ND row, int32 ``[B, num_nds, cols]``:
+    ``hist[b, r, c]`` = the number of points ``i`` with ``rows[b, i] == r`` and
+    ``labels[b, i] == c`` (``rows`` and ``labels`` int32 ``[B, N]``).  A point
+    whose row is outside ``0 .. num_nds - 1`` (-1: no row, padding) or whose
+    label is outside ``0 .. cols - 1`` or equals ``ignore_label`` (-1: none)
+    is left out.  The target of the point-level training loss
+    (``ndnet.training.point_loss``).  ``out`` is overwritten whole."""
+    _lib.require_gpu()
+    assert rows.is_cuda and rows.dtype == torch.int32 and rows.dim() == 2
+    assert labels.dtype == torch.int32 and labels.shape == rows.shape and labels.device == rows.device
+    rows, labels = rows.contiguous(), labels.contiguous()
+    B, n = rows.shape
+    k, cols = int(num_nds), int(cols)
+    if out is None:
+        out = torch.empty((B, k, cols), dtype=torch.int32, device=rows.device)
+    assert out.is_contiguous() and out.dtype == torch.int32 and out.device == rows.device and out.shape == (B, k, cols)
+    rc = _lib.lib().ndnet_seg_row_hist(rows.data_ptr(), labels.data_ptr(), B, n, k, cols, int(ignore_label),
+                                       out.data_ptr(), _lib.stream_ptr(rows.device))
+    _lib.check(rc, "ndnet_seg_row_hist")
+    return out
 
 
 def iou(conf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -50,6 +50,12 @@ def main() -> None:
     ap.add_argument("--no-save", action="store_true")
     ap.add_argument("--graphs", action="store_true",
                     help="one GPU: replay each training step from a captured HIP graph (Trainer(graphs=True))")
+    ap.add_argument("--loss", default="nds", choices=["nds", "points"],
+                    help="nds: the NLL of each ND's hard class; points: the mean NLL of every labelled point "
+                         "under the ND row it was folded into (Trainer(loss=...))")
+    ap.add_argument("--point-fill", default="nearest", choices=["nearest", "none"],
+                    help="loss=points: the row of a point of a pruned ND")
+    ap.add_argument("--ignore-label", type=int, default=-1, help="loss=points: a label left out of the loss")
     args = ap.parse_args()
     if args.task != "segmentation":
         raise NotImplementedError("only the segmentation task is on the hot path (train.py:122-123)")
@@ -62,7 +68,8 @@ def main() -> None:
     model = NDTNetSegmentation(3, args.n_classes, args.feature_dim)
     if args.graphs and world > 1:
         raise SystemExit("--graphs runs on one GPU (the DDP all-reduce is not captured)")
-    tr = Trainer(model, args.learning_rate, args.n_desired_nds, args.n_classes, dev, graphs=args.graphs)
+    tr = Trainer(model, args.learning_rate, args.n_desired_nds, args.n_classes, dev, graphs=args.graphs,
+                 loss=args.loss, point_fill=args.point_fill, ignore_label=args.ignore_label)
     path = os.path.join(args.out_path, datetime.datetime.now().strftime("%Y%m%d_%H%M%S"))
 
     loaders = {}
