@@ -46,6 +46,26 @@ class NdtStats(ctypes.Structure):
 STATS_BYTES = ctypes.sizeof(NdtStats)
 assert STATS_BYTES == 96
 
+
+class AugConfig(ctypes.Structure):
+    """ndnet_aug_config (include/ndnet_augment.h)."""
+    _fields_ = [
+        ("seed", ctypes.c_uint32),
+        ("stream", ctypes.c_uint32),
+        ("yaw_max", ctypes.c_double),
+        ("scale_lo", ctypes.c_double),
+        ("scale_hi", ctypes.c_double),
+        ("shift_max", ctypes.c_double * 3),
+        ("drop_max", ctypes.c_double),
+        ("jitter_sigma", ctypes.c_double),
+        ("flip_x_16", ctypes.c_uint32),
+        ("flip_y_16", ctypes.c_uint32),
+    ]
+
+
+assert ctypes.sizeof(AugConfig) == 80
+AUG_TILE = 1024  # NDNET_AUG_TILE (include/ndnet_augment.h)
+
 _lib = None
 
 _P = ctypes.c_void_p
@@ -99,6 +119,9 @@ EXPORTS = {
     # include/ndnet_fps.h
     "ndnet_fps_run": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
     "ndnet_fps_run_f64": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
+    # include/ndnet_augment.h
+    "ndnet_aug_work_bytes": (ctypes.c_size_t, [_I, _U64]),
+    "ndnet_aug_run": (_I, [_P, _P, _P, _P, _I, _U64, _P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_debug_dump": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_debug_set_epoch": (_I, [_P, ctypes.c_uint32]),
     "ndnet_ndt_debug_set_kl_fuse": (_I, [_P, _I]),

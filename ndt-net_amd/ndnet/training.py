@@ -220,7 +220,15 @@ class Trainer:
 
     DDP needs nothing more for the point loss: it is a per-rank scalar,
     normalised by the rank's own ``W``, and the gradients are averaged over
-    the ranks as before."""
+    the ranks as before.
+
+    ``augment`` (an ``ndnet.augment.Augment``): every training step -- eager or
+    captured, never the eval step -- first augments its points, class ids and
+    counts on the GPU; the labelled NDT run and the point loss then see the
+    augmented batch.  With ``drop > 0`` the step runs the ragged path on the
+    augmentation's device counts; with ``drop == 0`` and no ``counts`` it stays
+    on the fixed-size path.  A ``stream`` left open becomes the rank, so every
+    DDP rank draws its own augmentations from one seed."""
 
     LOSSES = ("nds", "points")
     POINT_FILLS = ("nearest", "none")
@@ -228,9 +236,14 @@ class Trainer:
     def __init__(self, model: torch.nn.Module, lr: float, num_nds: int, num_classes: int,
                  device: torch.device, ddp: Optional[bool] = None, bucket_cap_mb: float = 4.0,
                  graphs: bool = False, loss: str = "nds", point_fill: str = "nearest",
-                 ignore_label: int = -1) -> None:
+                 ignore_label: int = -1, augment=None) -> None:
         if loss not in self.LOSSES:  # (checked before any GPU work)
             raise ValueError(f"loss must be one of {self.LOSSES}, got {loss!r}")
+        if augment is not None:
+            from .augment import Augment
+            if not isinstance(augment, Augment):
+                raise ValueError(f"augment must be an ndnet.augment.Augment, got {type(augment).__name__}")
+        self.augment = augment
         if point_fill not in self.POINT_FILLS:
             raise ValueError(f"point_fill must be one of {self.POINT_FILLS}, got {point_fill!r}")
         self.loss, self.point_fill, self.ignore_label = loss, point_fill, int(ignore_label)
@@ -256,6 +269,8 @@ class Trainer:
             self.opt = HipAdam(self.model.parameters(), lr=torch.tensor(self.base_lr, device=device))
         else:
             self.opt = torch.optim.Adam(self.model.parameters(), lr=self.base_lr)
+        if augment is not None:
+            augment.resolve_stream()  # (after the DDP set-up: the rank by default)
 
     def set_epoch(self, epoch: int) -> None:
         for g in self.opt.param_groups:
@@ -288,13 +303,22 @@ class Trainer:
                 loss = loss_fn(pred, target)
         return loss.item(), acc_fn(pred.detach(), target).item()
 
-    def nds_and_targets(self, points: torch.Tensor, gt_points: torch.Tensor, counts=None):
+    def nds_and_targets(self, points: torch.Tensor, gt_points: torch.Tensor, counts=None, *, augment: bool = False):
         """The labelled NDT run of a batch and the step's target: ``(pcl, covs,
         gt, hist)`` with ``hist`` None for ``loss="nds"``, else the rows' class
         histograms from the points' rows and labels (all on the GPU; the eager
-        and the captured step both run this)."""
-        from .preprocessing.ndtnet_preprocessing import check_class_ids, class_ids, ndt_preprocessing
+        and the captured step both run this).  ``augment=True`` (the training
+        steps) puts the trainer's ``Augment``, if it has one, in front: its
+        points, ids and counts take the inputs' place."""
+        from .preprocessing.ndtnet_preprocessing import check_class_ids, check_counts, class_ids, ndt_preprocessing
         check_class_ids(gt_points, points)
+        if augment and self.augment is not None:
+            if counts is not None:
+                check_counts(counts, points.shape[0], points.shape[1])
+            pts = points.to(device=self.device, dtype=torch.float32)
+            points, gt_points, kept = self.augment(pts, class_ids(gt_points, self.device), counts)
+            if counts is not None or self.augment.drop > 0:
+                counts = kept  # (else every cloud is whole: the fixed-size path)
         if self.loss == "nds":
             pcl, covs, gt = ndt_preprocessing(self.num_nds, points.to(self.device), gt_points.to(self.device),
                                               self.num_classes, counts=counts)
@@ -319,7 +343,7 @@ class Trainer:
         if train and self.graphs:
             loss, acc = self.step_graphed(points, gt_points, counts)
             return loss.item(), acc.item()
-        pcl, covs, gt, hist = self.nds_and_targets(points, gt_points, counts)
+        pcl, covs, gt, hist = self.nds_and_targets(points, gt_points, counts, augment=train)
         return self.step_on_nds(pcl, covs, gt, train, hist)
 
     def _graph_for(self, points_shape, gt_shape, ragged: bool = False) -> "GraphedTrainStep":
@@ -368,7 +392,10 @@ class GraphedTrainStep:
     MIOpen's algorithm choices, the gradients and Adam's moments), so a few
     steps run eagerly on a side stream first; the parameters, buffers and
     optimizer state are snapshotted before them and restored after the
-    capture, so the first replay is the trainer's first step."""
+    capture, so the first replay is the trainer's first step.  The trainer's
+    ``Augment`` runs inside the graph; its step counter is snapshotted and
+    restored with the weights, so the first replay is draw 0 and every replay
+    draws anew."""
 
     def __init__(self, trainer: Trainer, points_shape, gt_width: Optional[int], warmup: int = 3,
                  ragged: bool = False) -> None:
@@ -392,6 +419,7 @@ class GraphedTrainStep:
             params = [p.detach().clone() for p in model.parameters()]
             bufs = [b.detach().clone() for b in model.buffers()]
             saved = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in opt.state.items()}
+            aug_step = tr.augment.step_tensor(dev).clone() if tr.augment is not None else None
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -417,11 +445,13 @@ class GraphedTrainStep:
                             v.copy_(before[k])
                         else:
                             v.zero_()  # a fresh moment / step count
+            if aug_step is not None:
+                tr.augment.step_tensor(dev).copy_(aug_step)  # the warm-up's draws are rolled back
         torch.cuda.synchronize(dev)
 
     def _body(self):
         tr = self.tr
-        pcl, covs, gt, hist = tr.nds_and_targets(self.s_points, self.s_gt, self.s_counts)
+        pcl, covs, gt, hist = tr.nds_and_targets(self.s_points, self.s_gt, self.s_counts, augment=True)
         tr.model.train()
         pred = tr.net(pcl, covs)
         loss = segmentation_loss(pred, gt) if hist is None else point_loss(pred, hist)

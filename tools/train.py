@@ -56,6 +56,17 @@ def main() -> None:
     ap.add_argument("--point-fill", default="nearest", choices=["nearest", "none"],
                     help="loss=points: the row of a point of a pruned ND")
     ap.add_argument("--ignore-label", type=int, default=-1, help="loss=points: a label left out of the loss")
+    ap.add_argument("--augment", action="store_true",
+                    help="augment every training batch on the GPU (ndnet.augment.Augment; the rank is its stream)")
+    ap.add_argument("--aug-yaw", type=float, default=180.0, help="largest yaw about z, degrees")
+    ap.add_argument("--aug-scale", type=float, nargs=2, default=(0.95, 1.05), metavar=("LO", "HI"))
+    ap.add_argument("--aug-flip", type=float, nargs=2, default=(0.0, 0.5), metavar=("PX", "PY"),
+                    help="probabilities of mirroring x and y")
+    ap.add_argument("--aug-shift", type=float, nargs=3, default=(0.0, 0.0, 0.0), metavar=("SX", "SY", "SZ"))
+    ap.add_argument("--aug-jitter", type=float, default=0.0, help="standard deviation of the per-point noise")
+    ap.add_argument("--aug-drop", type=float, default=0.0,
+                    help="largest share of a cloud's points dropped (each cloud draws its own share below it)")
+    ap.add_argument("--aug-seed", type=int, default=0)
     args = ap.parse_args()
     if args.task != "segmentation":
         raise NotImplementedError("only the segmentation task is on the hot path (train.py:122-123)")
@@ -68,8 +79,14 @@ def main() -> None:
     model = NDTNetSegmentation(3, args.n_classes, args.feature_dim)
     if args.graphs and world > 1:
         raise SystemExit("--graphs runs on one GPU (the DDP all-reduce is not captured)")
+    augment = None
+    if args.augment:
+        import math
+        from ndnet.augment import Augment
+        augment = Augment(yaw=math.radians(args.aug_yaw), scale=tuple(args.aug_scale), flip=tuple(args.aug_flip),
+                          shift=tuple(args.aug_shift), jitter=args.aug_jitter, drop=args.aug_drop, seed=args.aug_seed)
     tr = Trainer(model, args.learning_rate, args.n_desired_nds, args.n_classes, dev, graphs=args.graphs,
-                 loss=args.loss, point_fill=args.point_fill, ignore_label=args.ignore_label)
+                 loss=args.loss, point_fill=args.point_fill, ignore_label=args.ignore_label, augment=augment)
     path = os.path.join(args.out_path, datetime.datetime.now().strftime("%Y%m%d_%H%M%S"))
 
     loaders = {}
