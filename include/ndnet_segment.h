@@ -26,6 +26,16 @@ extern "C" {
 int ndnet_seg_point_labels(const float *d_scores, const int32_t *d_point_rows, int B, uint64_t n, uint64_t k,
                            int cols, int32_t unassigned, int32_t *d_nd_labels, int32_t *d_point_labels, void *stream);
 
+/* The same with one byte per point -- what a serving loop copies back to the host: d_point_labels
+ * [B][n] uint8, any byte alignment; d_nd_labels stays int32.  Same argmax (the same kernel), same
+ * gather, `unassigned` where the row is < 0 or >= k.  The gather takes four consecutive points per
+ * thread (a 16-byte row load, a 4-byte label store) wherever a cloud's rows and labels are so
+ * aligned, and single points at a cloud's misaligned head and its tail.
+ * NDNET_ERR_ARG for a NULL pointer, B, n, k or cols < 1, cols > 255 (a class must fit a byte) or
+ * unassigned < cols (the marker must not be a class). */
+int ndnet_seg_point_labels_u8(const float *d_scores, const int32_t *d_point_rows, int B, uint64_t n, uint64_t k,
+                              int cols, uint8_t unassigned, int32_t *d_nd_labels, uint8_t *d_point_labels, void *stream);
+
 /* Confusion matrices up to this many classes are counted in a per-workgroup
  * LDS histogram (cols * cols + 1 counters of 32 bits: 15.5 KB at 63) flushed
  * with one 64-bit global atomic per non-zero counter; wider ones take a 64-bit

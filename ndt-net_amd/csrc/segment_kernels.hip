@@ -7,6 +7,8 @@
 //                       (coalesced), the wave reduces to the first maximum
 //   k_seg_point_labels  a thread per point: one coalesced int32 load and store,
 //                       the ND labels (4 k bytes per cloud) from cache
+//   k_seg_point_labels_u8  the same as bytes, four points per thread: a 16-byte
+//                       row load and a 4-byte label store (scalar head and tail)
 //   k_seg_confusion     grid-stride over the points; a per-workgroup LDS
 //                       histogram flushed with 64-bit global atomics, or one
 //                       64-bit global atomic per point for wide matrices
@@ -77,6 +79,51 @@ __global__ void __launch_bounds__(kSegThreads) k_seg_point_labels(const int32_t*
   const uint64_t b = blockIdx.y;
   const int32_t row = point_rows[b * n + i];
   point_labels[b * n + i] = row >= 0 && (uint64_t)row < k ? nd_labels[b * k + (uint64_t)row] : unassigned;
+}
+
+// The labels as bytes, kSegU8Width points per thread: cloud b (grid y) is cut
+// into a head of 0..3 points that brings its output to a 4-byte boundary
+// (thread 0, byte stores), groups of four points -- one 16-byte row load where
+// the rows of the first group are 16-byte aligned (then every group's are),
+// four 4-byte loads where not, and one 4-byte store of the four labels -- and a
+// tail of n' % 4 points (the thread after the last whole group, byte stores).
+// The cut is per cloud, so no group spans two clouds whatever b * n is; both
+// branches are uniform over the cloud.  A label is < cols <= 255: one byte.
+constexpr int kSegU8Width = 4;
+
+__global__ void __launch_bounds__(kSegThreads) k_seg_point_labels_u8(const int32_t* __restrict__ point_rows,
+                                                                   const int32_t* __restrict__ nd_labels, uint64_t n,
+                                                                   uint64_t k, uint32_t unassigned,
+                                                                   uint8_t* __restrict__ point_labels) {
+  const uint64_t b = blockIdx.y;
+  const int32_t* rows = point_rows + b * n;
+  const int32_t* nd = nd_labels + b * k;
+  uint8_t* out = point_labels + b * n;
+  uint64_t head = (uint64_t)(0 - (uintptr_t)out) & (kSegU8Width - 1);
+  if (head > n) head = n;
+  auto label = [&](int32_t row) -> uint32_t {
+    return row >= 0 && (uint64_t)row < k ? (uint32_t)nd[(uint64_t)row] & 0xffu : unassigned;
+  };
+  const uint64_t t = (uint64_t)blockIdx.x * kSegThreads + threadIdx.x;
+  if (t == 0) {
+    for (uint64_t i = 0; i < head; i++) out[i] = (uint8_t)label(rows[i]);
+    return;
+  }
+  const uint64_t i0 = head + (t - 1) * kSegU8Width;
+  if (i0 >= n) return;
+  if (i0 + kSegU8Width > n) {
+    for (uint64_t i = i0; i < n; i++) out[i] = (uint8_t)label(rows[i]);
+    return;
+  }
+  int32_t r0, r1, r2, r3;
+  if ((((uintptr_t)(rows + head)) & 15) == 0) {
+    const int4 v = *reinterpret_cast<const int4*>(rows + i0);
+    r0 = v.x, r1 = v.y, r2 = v.z, r3 = v.w;
+  } else {
+    r0 = rows[i0], r1 = rows[i0 + 1], r2 = rows[i0 + 2], r3 = rows[i0 + 3];
+  }
+  // (little-endian: point i0 is the word's lowest byte)
+  *reinterpret_cast<uint32_t*>(out + i0) = label(r0) | label(r1) << 8 | label(r2) << 16 | label(r3) << 24;
 }
 
 constexpr int kConfPPT = 8;        // points per thread per grid-stride round
@@ -155,6 +202,24 @@ int ndnet_seg_point_labels(const float* d_scores, const int32_t* d_point_rows, i
   k_seg_nd_argmax<<<(uint32_t)rblocks, kSegThreads, 0, st>>>(d_scores, rows, cols, d_nd_labels);
   k_seg_point_labels<<<dim3((uint32_t)pblocks, (uint32_t)B), kSegThreads, 0, st>>>(d_point_rows, d_nd_labels, n, k,
                                                                                   unassigned, d_point_labels);
+  SEG_HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_seg_point_labels_u8(const float* d_scores, const int32_t* d_point_rows, int B, uint64_t n, uint64_t k, int cols,
+                              uint8_t unassigned, int32_t* d_nd_labels, uint8_t* d_point_labels, void* stream) {
+  if (!d_scores || !d_point_rows || !d_nd_labels || !d_point_labels || B < 1 || n < 1 || k < 1 || cols < 1)
+    return NDNET_ERR_ARG;
+  if (cols > 255 || (int)unassigned < cols) return NDNET_ERR_ARG;  // a class is a byte; the marker is no class
+  // thread 0 of a cloud takes its head, the next ceil(n / 4) its groups and tail
+  const uint64_t rows = (uint64_t)B * k, threads = 1 + (n + kSegU8Width - 1) / kSegU8Width;
+  const uint64_t pblocks = (threads + kSegThreads - 1) / kSegThreads;
+  const uint64_t rblocks = (rows + kSegThreads / 64 - 1) / (kSegThreads / 64);
+  if (rblocks > 0x7fffffffull || pblocks > 0x7fffffffull || B > 65535) return NDNET_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  k_seg_nd_argmax<<<(uint32_t)rblocks, kSegThreads, 0, st>>>(d_scores, rows, cols, d_nd_labels);
+  k_seg_point_labels_u8<<<dim3((uint32_t)pblocks, (uint32_t)B), kSegThreads, 0, st>>>(
+      d_point_rows, d_nd_labels, n, k, (uint32_t)unassigned, d_point_labels);
   SEG_HIPCHK(hipGetLastError());
   return NDNET_OK;
 }

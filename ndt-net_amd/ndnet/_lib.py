@@ -114,6 +114,7 @@ EXPORTS = {
     "ndnet_ndt_point_rows_counts": (_I, [_P, _P, _P, _P, _U64, _I, _P, _P]),
     # include/ndnet_segment.h
     "ndnet_seg_point_labels": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_int32, _P, _P, _P]),
+    "ndnet_seg_point_labels_u8": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_uint8, _P, _P, _P]),
     "ndnet_seg_confusion": (_I, [_P, _P, _U64, _I, _P, _P]),
     "ndnet_seg_row_hist": (_I, [_P, _P, _I, _U64, _U64, _I, ctypes.c_int32, _P, _P]),
     # include/ndnet_fps.h

@@ -285,16 +285,68 @@ class PipelinedSegmentation:
     (``model.precision`` or ``pointnet_hip.PRECISION`` at construction), as
     ``GraphedSegmentation`` does.
 
-    Per-point labels (``GraphedSegmentation(point_labels=...)``) are not
-    offered here: the NDT plan's state is overwritten by the next batch's NDT
-    stage before this batch's forward ends, so the points' rows would have to
-    be taken in the NDT stage and carried through the ring with the row
-    blocks.
+    ``point_labels`` (``"none"`` or ``"nearest"``, the fill of
+    ``NdtPlan.point_rows``): per-point labels, for an ``NDTNetSegmentation``
+    without ``levels``.  The NDT plan's state is overwritten by the next
+    batch's NDT stage before this batch's forward ends, so the points' rows
+    are taken inside the NDT stage, right after the run and in the same stage
+    graph, into a ring of R int32 ``[batch, num_points]`` buffers
+    (``point_rows[j]``) that travels with the row blocks; the forward stage of
+    the next step ends with ``segment.point_labels`` on them.  ``labels[j]``
+    is slot j's static ``[batch, num_points]`` output next to ``out[j]``, in
+    ``label_dtype`` (int32 with -1 for a point without a row, or uint8 with
+    255: a quarter of the bytes to copy back), and ``point_labels`` the one of
+    the step last enqueued.  Labels lag one step, exactly as the log-probs do;
+    ``replay()`` and ``replay_steps()`` return the log-probs as ever.
+
+    ``ragged=True``: a ring of R int32 ``[batch]`` count buffers, initialised
+    to ``num_points``; ``counts`` is the one the next step reads, as ``points``
+    is for the points, and ``load_resident(points, counts)`` fills all of
+    them.  Cloud ``b`` of a step is the first ``counts[b]`` points of its
+    input, as ``ndt_preprocessing(..., counts=)`` defines it (padding points
+    get label -1 / 255).  The kernels read the counts at replay, so one set
+    of stage graphs serves any mix of lengths up to ``num_points`` -- with
+    ``levels`` and with ``point_labels`` too.  Counts given as a CPU tensor or
+    a sequence are range-checked (``ValueError``); a device tensor is not.
+
+    ``replay_streamed(host_next, counts_next, labels_host)`` copies the next
+    batch's counts in with its points and this step's labels out to pinned
+    host memory, both beside the compute; wait on ``labels_copied`` before
+    reading ``labels_host``.
+
+    Ring order of the points' rows: ``point_rows[j]`` is written by the NDT
+    stage of slot j (step i), read by the forward of slot j + 1 (step i + 1)
+    alone, and next written by the NDT stage of step i + R -- which waits on
+    ``fwd_done[(j + 1) % R]``, last recorded by step i + 1's forward (slot
+    j + 1 is not used again before step i + R + 1).  That is the wait that
+    already orders the row blocks, for every F and N.  ``inputs[j]`` is read
+    by the NDT stage alone (the run and ``k_point_rows``), so
+    ``replay_streamed``'s copy waits on ``ndt_done`` as before.  ``labels[j]``
+    is written on forward stream j % F only (R is a multiple of F: stream
+    order), and a forward waits for the device-to-host copy of the labels it
+    overwrites.  Every stage graph stays one linear chain on its own stream.
     """
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,
                  device: Optional[torch.device] = None, warmup: int = 2, cu_share: Optional[int] = None,
-                 levels=None, fwd_streams: Optional[int] = None, ndt_streams: Optional[int] = None) -> None:
+                 levels=None, fwd_streams: Optional[int] = None, ndt_streams: Optional[int] = None,
+                 point_labels: Optional[str] = None, ragged: bool = False,
+                 label_dtype: torch.dtype = torch.int32) -> None:
+        if not isinstance(ragged, bool):  # (checked before any GPU work, as GraphedSegmentation's)
+            raise ValueError(f"ragged must be True or False, got {ragged!r}")
+        if label_dtype not in (torch.int32, torch.uint8):
+            raise ValueError(f"label_dtype must be torch.int32 or torch.uint8, got {label_dtype!r}")
+        if point_labels is not None:
+            from .models.ndtnet import NDTNetSegmentation
+            if point_labels not in _lib.POINT_FILL:
+                raise ValueError(f"point_labels must be None, 'none' or 'nearest', got {point_labels!r}")
+            if not isinstance(model, NDTNetSegmentation):
+                raise ValueError("point_labels needs an NDTNetSegmentation (a classifier has no per-ND classes)")
+            if levels:
+                raise ValueError("point_labels is not available with levels")
+            if label_dtype == torch.uint8 and model.num_classes + 1 > 255:
+                raise ValueError(f"uint8 labels need num_classes + 1 <= 255 (255 marks a point without a row), "
+                                 f"got {model.num_classes + 1} columns")
         _lib.require_gpu()
         if model.training:
             raise ValueError("PipelinedSegmentation needs an eval-mode model")
@@ -317,6 +369,20 @@ class PipelinedSegmentation:
         self.inputs = [torch.zeros((batch, num_points, 3), dtype=torch.float32, device=dev) for _ in range(R)]
         self.rows = [[torch.zeros((batch, k, 12), dtype=torch.float32, device=dev)
                       for k in (self.levels or (self.num_nds,))] for _ in range(R)]
+        # ragged: the counts of slot j's batch, read by its NDT stage alone
+        self.ragged = ragged
+        self.count_bufs = [torch.full((batch,), num_points, dtype=torch.int32, device=dev)
+                           for _ in range(R)] if ragged else None
+        # point labels: the points' rows travel with the row blocks (written by
+        # slot j's NDT stage, read by slot j + 1's forward); the labels and the
+        # per-ND argmax scratch belong to the forward's slot
+        self.fill, self.label_dtype = point_labels, label_dtype
+        self.point_rows = self.labels = self._nd_labels = None
+        if point_labels is not None:
+            self.point_rows = [torch.full((batch, num_points), -1, dtype=torch.int32, device=dev) for _ in range(R)]
+            self.labels = [torch.full((batch, num_points), -1 if label_dtype == torch.int32 else 255,
+                                      dtype=label_dtype, device=dev) for _ in range(R)]
+            self._nd_labels = [torch.zeros((batch, self.num_nds), dtype=torch.int32, device=dev) for _ in range(R)]
         # plans of its own (not ndt_preprocessing's cached one): their CU share
         # is a property of the pipeline
         self.plans = [NdtPlan(batch, num_points, self.num_nds, -1, device=dev) for _ in range(N)]
@@ -366,6 +432,11 @@ class PipelinedSegmentation:
         self.ndt_done = [torch.cuda.Event() for _ in range(R)]  # NDT of slot j finished (rows j, input j free)
         self.fwd_done = [torch.cuda.Event() for _ in range(R)]  # forward of slot j finished (rows j - 1 free)
         self.copied = [torch.cuda.Event() for _ in range(R)]    # input j holds the streamed batch
+        # labels j copied to the host (replay_streamed): on a stream of its own, so
+        # the copy out, which waits for this step's forward, does not hold the copy in
+        self.s_out = torch.cuda.Stream(device=dev) if self.fill is not None else None
+        self.labels_out = [torch.cuda.Event() for _ in range(R)] if self.fill is not None else None
+        self.labels_copied = None                                # the event of the last such copy
         self._fork()
         with torch.no_grad():  # plan / workspace creation, kernel attributes
             for i in range(max(R, warmup)):
@@ -391,9 +462,14 @@ class PipelinedSegmentation:
     def _ndt(self, j: int) -> None:
         """The NDT stage of ring slot j on the current stream, with plan j % N."""
         rows, plan = self.rows[j], self.plans[j % self.N]
-        plan.run(self.inputs[j], None, rows[0], None)
+        counts = self.count_bufs[j] if self.ragged else None
+        plan.run(self.inputs[j], None, rows[0], None, counts=counts)
         for k, blk in zip(self.levels[1:] if self.levels else (), rows[1:]):
             plan.prune(k, blk)
+        if self.fill is not None:
+            # here, while plan j % N still holds this batch's state: the NDT stage
+            # of step i + N overwrites it, possibly before this batch's forward ends
+            plan.point_rows(self.inputs[j], rows[0], self.num_nds, self.fill, out=self.point_rows[j], counts=counts)
 
     def _fwd(self, j: int):
         """The forward stage of ring slot j: the rows of slot j - 1, in
@@ -401,6 +477,9 @@ class PipelinedSegmentation:
         from .models import pointnet_hip
         with pointnet_hip.workspace_slot(j % self.F):
             outs = [self.model(r[..., :3], r[..., 3:]) for r in self.rows[(j - 1) % self.R]]
+        if self.fill is not None:
+            segment.point_labels(outs[0], self.point_rows[(j - 1) % self.R], out=self.labels[j],
+                                 nd_labels=self._nd_labels[j])
         return outs if self.levels else outs[0]
 
     def _enqueue(self) -> int:
@@ -408,10 +487,12 @@ class PipelinedSegmentation:
         R, j = self.R, self.i % self.R
         s_fwd = self.s_fwds[j % self.F]
         s_fwd.wait_event(self.ndt_done[(j - 1) % R])         # its rows: the previous step's NDT
+        if self.fill is not None:
+            s_fwd.wait_event(self.labels_out[j])            # no-op unless a streamed copy reads labels j
         with torch.cuda.stream(s_fwd):
             self.g_fwd[j].replay()
         self.fwd_done[j].record(s_fwd)
-        # rows j: last read by the forward of step i - R + 1
+        # rows j (and the points' rows j): last read by the forward of step i - R + 1
         s_ndt = self.s_ndts[j % self.N]
         s_ndt.wait_event(self.fwd_done[(j + 1) % R])
         s_ndt.wait_event(self.copied[j])                    # no-op unless a streamed copy targets input j
@@ -439,10 +520,33 @@ class PipelinedSegmentation:
         """The input buffer the next step reads."""
         return self.inputs[self.i % self.R]
 
-    def load_resident(self, points: torch.Tensor) -> None:
-        """Fill every input buffer (every later step re-reads this batch)."""
+    @property
+    def counts(self) -> Optional[torch.Tensor]:
+        """The count buffer the next step reads (``ragged=True``; else None)."""
+        return self.count_bufs[self.i % self.R] if self.ragged else None
+
+    @property
+    def point_labels(self) -> Optional[torch.Tensor]:
+        """The label buffer of the step last enqueued (``point_labels=``; else None)."""
+        return self.labels[(self.i - 1) % self.R] if self.fill is not None else None
+
+    def _host_counts(self, counts) -> torch.Tensor:
+        """Counts as an int32 tensor, range-checked unless they are on the device."""
+        if not self.ragged:
+            raise ValueError("counts need a pipeline built with ragged=True")
+        check_counts(counts, self.inputs[0].shape[0], self.inputs[0].shape[1])
+        return torch.as_tensor(counts).to(torch.int32)
+
+    def load_resident(self, points: torch.Tensor, counts=None) -> None:
+        """Fill every input buffer (every later step re-reads this batch) and,
+        with ``counts``, every count buffer (None leaves them as they are)."""
+        if counts is not None:
+            counts = self._host_counts(counts)
         for buf in self.inputs:
             buf.copy_(points)
+        if counts is not None:
+            for buf in self.count_bufs:
+                buf.copy_(counts)
 
     def replay(self):
         """One step, ordered after the caller's stream and before its later work."""
@@ -465,15 +569,41 @@ class PipelinedSegmentation:
         self._join(j)
         return self.out[j]
 
-    def replay_streamed(self, host_next: torch.Tensor):
-        """``replay()`` with the H2D copy of the batch after it overlapped."""
-        nxt = (self.i + 1) % self.R
+    def replay_streamed(self, host_next: torch.Tensor, counts_next=None, labels_host: Optional[torch.Tensor] = None):
+        """``replay()`` with the H2D copy of the batch after it overlapped.
+
+        ``counts_next`` (``ragged=True``): that batch's counts, a CPU tensor,
+        range-checked (``ValueError``) and copied in with its points.
+        ``labels_host`` (``point_labels=``): a pinned tensor of the labels'
+        shape and dtype that receives this step's labels (the batch before
+        this step's) on a copy stream of its own, after this step's forward;
+        ``labels_copied`` is that copy's event, for the caller to wait on."""
+        if counts_next is not None:
+            counts_next = self._host_counts(counts_next)
+        if labels_host is not None:
+            if self.fill is None:
+                raise ValueError("labels_host needs a pipeline built with point_labels")
+            ref = self.labels[0]
+            if labels_host.shape != ref.shape or labels_host.dtype != ref.dtype or not labels_host.is_pinned():
+                raise ValueError(f"labels_host must be a pinned {ref.dtype} tensor of shape {tuple(ref.shape)}")
+        j, nxt = self.i % self.R, (self.i + 1) % self.R
         out = self.replay()
-        # input nxt: last read by the NDT of step i + 1 - R, finished before this step's join
+        # input nxt: last read by the NDT of step i + 1 - R (the run and k_point_rows,
+        # both inside the NDT stage), finished before this step's join
         self.s_copy.wait_event(self.ndt_done[nxt])
         with torch.cuda.stream(self.s_copy):
             self.inputs[nxt].copy_(host_next, non_blocking=True)
+            if counts_next is not None:
+                self.count_bufs[nxt].copy_(counts_next, non_blocking=True)
             self.copied[nxt].record(self.s_copy)
+        if labels_host is not None:
+            # labels j: written by this step's forward, next by the forward of step
+            # i + R, which waits for labels_out[j] (_enqueue)
+            self.s_out.wait_event(self.fwd_done[j])
+            with torch.cuda.stream(self.s_out):
+                labels_host.copy_(self.labels[j], non_blocking=True)
+                self.labels_out[j].record(self.s_out)
+            self.labels_copied = self.labels_out[j]
         return out
 
     def stats(self) -> list:

@@ -55,13 +55,38 @@ def point_rows(points: torch.Tensor, fill: str = "none", plan: Optional[NdtPlan]
     return plan.point_rows(pts, rows_block, k, fill, out, counts=counts)
 
 
-def point_labels(scores: torch.Tensor, rows: torch.Tensor, unassigned: int = -1,
-                 out: Optional[torch.Tensor] = None, nd_labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _label_args(cols: int, unassigned: Optional[int], out: Optional[torch.Tensor], dtype) -> Tuple[torch.dtype, int]:
+    """The label dtype (``out``'s when given) and the unassigned marker of
+    ``point_labels``, checked on the host (``ValueError``)."""
+    if out is not None:
+        dtype = out.dtype
+    if dtype not in (torch.int32, torch.uint8):
+        raise ValueError(f"point labels are int32 or uint8, got {dtype}")
+    if dtype == torch.int32:
+        return dtype, -1 if unassigned is None else int(unassigned)
+    if cols > 255:
+        raise ValueError(f"uint8 labels hold at most 255 columns, got {cols}")
+    unassigned = 255 if unassigned is None else int(unassigned)
+    if not cols <= unassigned <= 255:
+        raise ValueError(f"the uint8 unassigned marker must lie in {cols} .. 255 (no class), got {unassigned}")
+    return dtype, unassigned
+
+
+def point_labels(scores: torch.Tensor, rows: torch.Tensor, unassigned: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None, nd_labels: Optional[torch.Tensor] = None,
+                 dtype: torch.dtype = torch.int32) -> torch.Tensor:
     """``labels[b, i] = argmax(scores[b, rows[b, i]])``, int32 ``[B, N]``;
     ``unassigned`` where ``rows[b, i] < 0``.  ``scores`` ``[B, k, C + 1]``
     float32 (log-probs or any per-ND scores), ``rows`` ``[B, N]`` int32.  The
     argmax runs once per ND (first maximum, NaN as a maximum, as
-    ``torch.argmax``); ``nd_labels`` ``[B, k]`` int32 receives it."""
+    ``torch.argmax``); ``nd_labels`` ``[B, k]`` int32 receives it.
+
+    ``dtype=torch.uint8`` (or a uint8 ``out``, whose dtype wins): one byte per
+    point, a quarter of the bytes to copy back to the host.  ``unassigned``
+    defaults to -1 for int32 and to 255 for uint8, where it must be no class:
+    more than 255 columns or a marker below the column count is a
+    ``ValueError``, raised before any GPU work."""
+    dtype, unassigned = _label_args(scores.shape[-1], unassigned, out, dtype)
     _lib.require_gpu()
     assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3
     assert rows.dtype == torch.int32 and rows.dim() == 2 and rows.device == scores.device
@@ -70,14 +95,15 @@ def point_labels(scores: torch.Tensor, rows: torch.Tensor, unassigned: int = -1,
     B, k, cols = scores.shape
     n = rows.shape[1]
     if out is None:
-        out = torch.empty((B, n), dtype=torch.int32, device=scores.device)
+        out = torch.empty((B, n), dtype=dtype, device=scores.device)
     if nd_labels is None:
         nd_labels = torch.empty((B, k), dtype=torch.int32, device=scores.device)
-    for t, shape in ((out, (B, n)), (nd_labels, (B, k))):
-        assert t.is_contiguous() and t.dtype == torch.int32 and t.device == scores.device and t.shape == shape
-    rc = _lib.lib().ndnet_seg_point_labels(scores.data_ptr(), rows.data_ptr(), B, n, k, cols, int(unassigned),
-                                           nd_labels.data_ptr(), out.data_ptr(), _lib.stream_ptr(scores.device))
-    _lib.check(rc, "ndnet_seg_point_labels")
+    for t, shape, dt in ((out, (B, n), dtype), (nd_labels, (B, k), torch.int32)):
+        assert t.is_contiguous() and t.dtype == dt and t.device == scores.device and t.shape == shape
+    name = "ndnet_seg_point_labels" if dtype == torch.int32 else "ndnet_seg_point_labels_u8"
+    rc = getattr(_lib.lib(), name)(scores.data_ptr(), rows.data_ptr(), B, n, k, cols, unassigned,
+                                   nd_labels.data_ptr(), out.data_ptr(), _lib.stream_ptr(scores.device))
+    _lib.check(rc, name)
     return out
 
 
