@@ -305,33 +305,6 @@ NDNET_FN int lu3_sgndet(const double* LU, int signum) {
   return s;
 }
 
-#ifdef NDNET_LU_INVERT_COLUMNS
-// Variant (round 1): inverse from LU column by column (P e_j, unit-lower
-// forward, upper back substitution in gslcblas dtrsv order).  Rounds
-// differently from GSL 2.7.1's LU_invert below (<= 3.7e-13 relative on a KL
-// score); kept for A/B runs only.
-NDNET_FN void lu3_invert(const double* LU, uint32_t perm_packed, double* inv) {
-  int perm[3] = {(int)(perm_packed & 3), (int)((perm_packed >> 2) & 3), (int)((perm_packed >> 4) & 3)};
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    double x0 = (perm[0] == j) ? 1.0 : 0.0;
-    double x1 = (perm[1] == j) ? 1.0 : 0.0;
-    double x2 = (perm[2] == j) ? 1.0 : 0.0;
-    x1 = x1 - LU[3] * x0;
-    x2 = x2 - LU[6] * x0;
-    x2 = x2 - LU[7] * x1;
-    x2 = x2 / LU[8];
-    x1 = x1 - LU[5] * x2;
-    x1 = x1 / LU[4];
-    double t = x0 - LU[1] * x1;
-    t = t - LU[2] * x2;
-    x0 = t / LU[0];
-    inv[0 * 3 + j] = x0;
-    inv[1 * 3 + j] = x1;
-    inv[2 * 3 + j] = x2;
-  }
-}
-#else
 // gsl_linalg_LU_invert as GSL 2.7.1 publishes it (linalg/lu.c): the inverse
 // is the LU copy run through gsl_linalg_LU_invx --
 //   1. gsl_linalg_tri_invert(CblasUpper, CblasNonUnit): U^-1 in place
@@ -419,7 +392,6 @@ NDNET_FN void lu3_invert(const double* LU, uint32_t perm_packed, double* inv) {
     }
   }
 }
-#endif
 
 // kullback_leibler.c:98-115 given both operands already decomposed:
 // 0.5 * (0 + tr(inv_q * LU_p) - log(det_q / det_p) - 3), the trace summed as

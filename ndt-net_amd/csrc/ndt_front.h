@@ -1,7 +1,8 @@
 // ndt_front.h -- k_front: the whole front of ndt_downsample in ONE launch.
 //
-// Included by ndt_kernels.hip inside its anonymous namespace (it uses
-// CloudCtl, voxel_key, the block scans and finish_pass from there).
+// Included by ndt_kernels.hip inside its anonymous namespace, after ndt_plan.h
+// (CloudCtl, the constants), ndt_block.h (the block scans) and the path-1
+// kernels of ndt_kernels.hip (voxel_key, finish_pass).
 //
 // What it replaces, per cloud (reference: pointclouds.c:40-66 limits,
 // ndt.c:136-194 bisection over estimate_ndt's occupancy,
@@ -51,15 +52,6 @@ constexpr int kFrontWaves = kFrontThreads / 64;
 #define NDNET_FRONT_R 8
 #endif
 constexpr int kFrontR = NDNET_FRONT_R;  // bins per workgroup whose points stay in registers
-#ifndef NDNET_FRONT_BYTEMAP_READ
-#define NDNET_FRONT_BYTEMAP_READ 0  // 1: read a voxel's byte before marking it (round 1-4 form)
-#endif
-#ifndef NDNET_FRONT_LDSMATCH
-#define NDNET_FRONT_LDSMATCH 1  // the rank loop's low ND-id bits matched through LDS slots
-#endif
-#ifndef NDNET_FRONT_HEAVYSORT
-#define NDNET_FRONT_HEAVYSORT 1  // 0: heavy NDs in listing order (A/B)
-#endif
 constexpr int kHeavySort = 256;     // heavy NDs per cloud that k_front lists by descending count
 constexpr int kFrontTable = 8192;   // LDS words: byte map of a small grid (32768 voxels) or hash slots
 constexpr int kFrontPhases = 40;    // record slots per cloud and run
@@ -335,14 +327,8 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
   int b;
   if (A.xcd_local) {
     const uint32_t slot = L / 8u;  // slot within the XCD
-#ifdef NDNET_FRONT_DEAL_MINOR  // A/B only: the round 2-5 deal (deadlocks two concurrent launches)
-    const uint32_t cpx = A.B / 8u;
-    b = (int)((slot % cpx) * 8u + L % 8u);
-    g = slot / cpx;
-#else
     b = (int)((slot / G) * 8u + L % 8u);
     g = slot % G;
-#endif
   } else {
     b = (int)(L / G);
     g = L % G;
@@ -591,11 +577,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
         redo |= key == kKeyRedo;
         cold |= key == kInvalid;
         if (small && key < kKeyRedo) {
-#if NDNET_FRONT_BYTEMAP_READ
-          if (!bytemap[key]) bytemap[key] = 1;  // read first: most lanes of a small grid hit set bytes
-#else
           bytemap[key] = 1;  // a plain store: no LDS round trip per point before the next point's key
-#endif
         }
       }
       binfo[j * 1024 + t] = key;
@@ -894,7 +876,6 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
     // m &= ~(ballot ^ mask) on both halves -- the lanes that agree on the bit.
     const uint32_t nbits = __builtin_amdgcn_readfirstlane(32u - (uint32_t)__clz((int)(ndcap > 1 ? ndcap - 1 : 1)));
     const unsigned long long below = (1ull << lane) - 1ull;
-#if NDNET_FRONT_LDSMATCH
     // Round 4: the low 8 bits of the ND id matched through LDS instead of 8
     // ballot rounds: each lane ORs its bit into its wave's slot d & 255
     // (the table region is free once the point NDs are found: 16 waves x 256
@@ -906,25 +887,18 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
 #pragma unroll
     for (int e = 0; e < 4; e++) slots[lane + 64 * e] = 0ull;
     const unsigned long long mybit = 1ull << lane;
-#endif
     for (uint32_t r = wave; r < nrb; r += kFrontWaves) {
       uint16_t* hr = hist + (uint64_t)r * ndcap;
       uint32_t* br = binfo + (uint64_t)r * rbs;
       for (uint32_t st = 0; st < rbs / 64; st++) {
         const uint32_t d = br[st * 64 + lane];
         const bool valid = d != kInvalid;
-#if NDNET_FRONT_LDSMATCH
         const uint32_t h = d & 255u;
         if (valid) __hip_atomic_fetch_or(&slots[h], mybit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         // the wave's ORs are one LDS instruction, executed before this read
         const unsigned long long mv = valid ? __hip_atomic_load(&slots[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0ull;
         uint32_t mlo = (uint32_t)mv, mhi = (uint32_t)(mv >> 32);
         constexpr uint32_t kBit0 = 8;
-#else
-        const unsigned long long mv = __ballot(valid);
-        uint32_t mlo = (uint32_t)mv, mhi = (uint32_t)(mv >> 32);
-        constexpr uint32_t kBit0 = 0;
-#endif
 #pragma unroll
         for (uint32_t bit = kBit0; bit < 15; bit++) {  // ndcap <= 16384 (k_front host check)
           if (bit < nbits) {
@@ -935,11 +909,9 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
           }
         }
         const unsigned long long m = ((unsigned long long)mhi << 32) | mlo;
-#if NDNET_FRONT_LDSMATCH
         // every lane of the slot has read it (the read above is one
         // instruction): cleared for the next step
         if (valid) __hip_atomic_store(&slots[h], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
         if (valid) {
           const uint32_t rank = (uint32_t)__popcll(m & below), cnt = (uint32_t)__popcll(m);
           const uint32_t cur = hr[d];  // read by every lane of the set before its last lane writes
@@ -1052,7 +1024,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
       c.heavy_n = s_heavy;
       c.heavy_t = A.heavy_t;
     }
-    if (NDNET_FRONT_HEAVYSORT && g == 0 && s_heavy > 1u && s_heavy <= (uint32_t)kHeavySort && t < s_heavy) {
+    if (g == 0 && s_heavy > 1u && s_heavy <= (uint32_t)kHeavySort && t < s_heavy) {
       // the cloud's heavy NDs by descending count: k_welford_q's first round
       // gives item i to wave i % 4 of workgroup i / 4, so a cloud's longest
       // NDs share a few workgroups (CUs) instead of each holding one CU to
@@ -1103,14 +1075,7 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
         float3* o3 = reinterpret_cast<float3*>(out);
         for (uint32_t l = t; l < lcarry; l += kFrontThreads) {
           const float4 r = rec[l];
-#ifdef NDNET_FRONT_STAGED_NT  // A/B: streaming (nontemporal) stores
-          float* o = reinterpret_cast<float*>(o3 + __float_as_uint(r.w));
-          __builtin_nontemporal_store(r.x, o);
-          __builtin_nontemporal_store(r.y, o + 1);
-          __builtin_nontemporal_store(r.z, o + 2);
-#else
           o3[__float_as_uint(r.w)] = make_float3(r.x, r.y, r.z);
-#endif
         }
       }
     }

@@ -9,22 +9,49 @@
 // the stride between clouds and cloud b its first counts[b] points (DESIGN.md
 // §3 "Ragged batches").
 //
-// Kernels, in launch order (see DESIGN.md for the data layout and rooflines):
-//   k_reset        per-cloud control block for this call
-//   k_limits       bounding box (pointclouds.c:40-66), first grid
-//   k_search_pass  one bisection pass: voxel keys of all points, distinct
-//                  occupied voxels counted through per-voxel stamps; the last
-//                  workgroup of a cloud applies ndt.c:169-187.  Launched 15x.
-//   k_dense        occupied voxels of the accepted grid -> dense ids in
-//                  ascending linear order (the output order, ndt.c:88-90)
-//   k_chunk_sort   stable per-chunk sort of points by dense id
-//   k_welford      a lane quad per ND, sequential Welford in point order
-//                  (normal_distributions.c:75-121), bit-exact
-//   k_kl           one workgroup per cloud: LU chains, KL events, the
-//                  reference's insertion order, prune, compaction
-//   k_prune        a further prune level on the retained list (ndt.c:28-73)
-//   k_point_rows   after a run or a prune level, on request: the output row
-//                  every input point was folded into (ndnet_ndt_point_rows)
+// Kernels, in launch order (see DESIGN.md for the data layout and rooflines);
+// they are defined below unless a header is named.  The ndt_*.h headers other
+// than ndt_device.h and ndt_log*.h are included once each, inside this file's
+// anonymous namespace: one translation unit, one set of flags.  ndt_plan.h has
+// the constants, CloudCtl and Plan; ndt_block.h the scans every stage shares.
+// The front of a run, path 2 (the default where the plan's shape admits it):
+//   k_front           ndt_front.h: limits, the bisection, dense ids and the
+//                     binning of every point to its ND's run, in one launch
+//                     (admitted through the front lanes: ndt_front_lanes.h)
+// or path 1, the same in separate launches:
+//   k_reset           per-cloud control block for this call
+//   k_limits          bounding box (pointclouds.c:40-66), first grid
+//   k_search_pass     one bisection pass: voxel keys of all points, distinct
+//                     occupied voxels counted through bitmaps or per-voxel
+//                     stamps; the last workgroup of a cloud applies
+//                     ndt.c:169-187.  Launched 15x.
+//   k_dense           occupied voxels of the accepted grid -> dense ids in
+//                     ascending linear order (the output order, ndt.c:88-90)
+//   k_bin_count, k_bin_offsets, k_bin_scatter
+//                     the points grouped by ND, in index order
+// Then, for both paths:
+//   k_welford_q       per-ND sequential Welford in point order
+//                     (normal_distributions.c:75-121), bit-exact; class
+//                     histograms; the LU chains of every 64-ND group
+//   k_kl_rank_chunks  the KL events scored and ranked per chunk
+//   k_kl_nan_keys     the NaN events' keys (lists past the merge's LDS)
+//   k_kl_merge        the chunks merged into the reference's insertion order;
+//                     its tail form also prunes and emits
+//   k_kl_sort         one workgroup per cloud instead of the merge, where the
+//                     list fits its LDS (sort_fits); k_kl_rank_sort: the
+//                     ranks and the sort in one launch
+//   k_kl              prune, compaction and the output rows, where the merge
+//                     or sort launch did not carry them (kl_fusable)
+// After a run, on request:
+//   k_kl_chains       ndt_prune.h: the LU chain states of the retained lists
+//                     a lazy run deferred, before the list sort above and
+//                     k_kl_list_done build them (build_deferred_lists)
+//   k_prune           ndt_prune.h: a further prune level on the retained list
+//                     (ndt.c:28-73)
+//   k_point_rows      ndt_point_rows.h: the output row every input point was
+//                     folded into (ndnet_ndt_point_rows)
+//   k_set_epoch, k_debug_lu_chain
+//                     debug entry points
 //
 // The translation unit is compiled with -ffp-contract=off: every double
 // operation rounds exactly like the reference's x86-64 build.
@@ -46,261 +73,8 @@ using namespace ndnet;
 
 namespace {
 
-constexpr int kPassThreads = 256;    // threads per search workgroup
-constexpr int kPassPPT = 4;          // points per thread per search workgroup
-constexpr int kPassPts = kPassThreads * kPassPPT;
-constexpr int kHashSlots = 2048;     // LDS dedup table of a search workgroup (>= kBitsWords)
-constexpr int kBitsCap = 32768;      // grids up to this many voxels count through bitmaps
-constexpr int kBitsWords = kBitsCap / 32;
-constexpr int kKLThreads = 1024;
-constexpr int kChunk = 256;          // slots per chunk of the chip-wide event sort
-constexpr int kKLMarks = 32;  // phase stamps per cloud of the KL kernels (timing level 2)
-constexpr int kMergeLdsChunks = 34;  // k_kl_merge stages score + NaN keys in LDS up to this many chunks (136 KB)
-constexpr int kMergeScoreChunks = 72; // ... and the score runs alone up to this many (144 KB; k <= 2440)
-constexpr int kMaxChunks = 6 * 16384 / kChunk;  // ndcap <= 16384
-// NDs with at least this many samples get a whole wave each in k_welford_q
-// (wq_heavy): k_front / k_bin_offsets list them per cloud.  The plan's
-// default (ndnet_ndt_set_heavy_threshold).
-#ifndef NDNET_WQ_HEAVY
-#define NDNET_WQ_HEAVY 256
-#endif
-constexpr uint32_t kWqHeavy = NDNET_WQ_HEAVY;
-
-enum State : uint32_t { kSearching = 0, kAccepted = 1, kFailed = 2 };
-
-struct CloudCtl {
-  unsigned long long limkey[6];  // order keys: max x,y,z then min x,y,z
-  double lim[6];
-  double guess, lo, hi;
-  double vs;
-  double off[3];
-  uint32_t len[3];
-  uint32_t state;
-  int32_t rc;
-  uint32_t iter;
-  uint32_t epoch;
-  uint32_t stamp;
-  uint32_t accepted_stamp;
-  uint32_t acc_mode;     // occupancy of the accepted pass: 0/1 bitmap buffer, 2 stamps
-  uint32_t count;
-  uint32_t arrive;
-  uint32_t nbad;
-  uint32_t first_bad[kWorkers];
-  uint64_t V;
-  uint32_t num_nds;
-  double guesses[16];
-  uint32_t counts[16];
-  // list state kept for further prune levels (ndt_legacy.py:173-240)
-  uint32_t num_valid;
-  uint32_t num_kl;       // live list length
-  uint32_t num_phys;     // entries ever written (the rest is poison)
-  uint32_t num_events;
-  int32_t prune_rc;
-  uint32_t num_out;
-  uint32_t last_k;
-  uint32_t clear_stamps; // the epoch wrapped this run: k_limits zeroes the cloud's stamps
-  uint32_t kl_deferred;  // the retained list was not built by the run (lazy list, num_nds <= k)
-  uint32_t flag_count;   // events of a deferred cloud, counted by k_kl_rank_chunks (zeroed per run)
-  uint32_t list_off;     // physical index of the retained list's first entry (the prunes' pending
-                         // left shifts, ndt.c:69-72; always 0 on the global-memory prune path)
-  uint32_t heavy_n;      // NDs of the accepted grid with >= kWqHeavy samples, listed in Plan::heavy
-                         // (written by the binning of every run that accepts a grid)
-  uint32_t heavy_t;      // the threshold that list was built with: k_welford_q's light items skip
-                         // exactly the NDs it holds, whatever the plan's threshold is by then
-  uint32_t kl_arrive;    // k_kl_merge<.., kTail> workgroups of the cloud done (re-armed by the last)
-};
-
-struct Plan {
-  int B;
-  uint64_t n;
-  uint64_t k;
-  int ncls;            // num_classes (histograms have ncls+1 bins)
-  uint64_t vcap;       // voxels per cloud the stamp / dense tables hold
-  uint32_t ndcap;      // max accepted NDs per cloud = floor(1.2 k) + 1
-  uint32_t ecap;       // 6 * ndcap
-  uint32_t nbins;      // 1024-point binning chunks per cloud
-  uint32_t G;          // search workgroups per cloud
-  int in_f64;          // input element type of the last run
-  uint64_t calls;      // runs issued from the host (graph replays not counted)
-  int timing;          // 0 off, 1 stage events, 2 + k_kl phase marks
-  int ev_created;
-  hipEvent_t ev[8];
-  unsigned long long* kl_marks;  // [B][kKLMarks] s_memrealtime stamps (timing level 2)
-  unsigned long long* wq_marks;  // [wq_items][kWqMarkW] k_welford_q per-item stamps (timing level 2)
-  // device buffers
-  CloudCtl* ctl;
-  uint32_t* stamps;    // [B][vcap]
-  uint32_t* dense_of;  // [B][vcap]
-  uint32_t* vox;       // [B][ndcap] linear index of dense id
-  uint32_t* gbits;     // [B][2][kBitsWords] occupancy bitmaps of small-grid passes
-  uint32_t* pkeys;     // [B][n] voxel key of every point in the latest pass
-  uint32_t* did;       // [B][n] dense id of every point in the accepted pass
-  uint32_t* bin_cnt;   // [B][nbins][ndcap] per-chunk histograms -> offsets
-  uint32_t* nd_base;   // [B][ndcap]
-  void* nd_pts;        // [B][n][3] points grouped by ND (input element type)
-  uint16_t* nd_lbl;    // [B][n]
-  uint32_t* nd_n;      // [B][ndcap]
-  double* nd_mean;     // [B][ndcap][3]
-  double* nd_cov;      // [B][ndcap][9] pre-KL
-  double* nd_cov_post; // [B][ndcap][9]
-  uint16_t* nd_cls;    // [B][ndcap]
-  uint32_t* hist;      // [B][ndcap][ncls+1]
-  int32_t* nb;         // [B][ndcap][6]
-  uint32_t* keys;      // [B][ndcap][12]
-  uint32_t* nkeys;     // [B][ndcap]
-  double* chain;       // [B][ndcap][12][9]
-  uint32_t* chain_ps;  // [B][ndcap][12] perm | (signum < 0) << 8
-  uint32_t* chain_ok;  // [B][ndcap] bit t: LU state t has det != 0 and sgndet != 0 (lazy clouds only)
-  double* slot_val;    // [B][ecap]
-  uint32_t* slot_flag; // [B][ecap]
-  double* ev_val;      // [B][ecap]
-  uint32_t* ev_p;      // [B][ecap]
-  uint32_t* ev_q;      // [B][ecap]
-  double* ev_min;      // [B][ecap] exclusive prefix min (NaN-skipping)
-  unsigned long long* sort_key;  // [B][sortcap]
-  uint32_t* sort_idx;  // [B][sortcap]
-  uint32_t* nan_list;  // [B][ecap] NaN slots per chunk (chunk * kChunk + j)
-  unsigned long long* nan_key;  // [B][ecap] NaN keys, contiguous in slot order
-  uint32_t* nan_slot;  // [B][ecap] their slots
-  uint32_t* chunk_nanbase;  // [B][nchunk] NaN events in earlier chunks
-  double* ord_val;     // [B][ecap] the retained list (physical array)
-  uint32_t* ord_p;     // [B][ecap]
-  uint32_t* ord_q;     // [B][ecap]
-  uint32_t* first_occ; // [B][ndcap]
-  uint32_t* tmp_u32;   // [B][ecap] scratch
-  uint8_t* alive;      // [B][ndcap]
-  uint32_t sortcap;    // chunked sort arrays per cloud: roundup(ecap, kChunk)
-  uint32_t nchunk;     // kChunk-slot chunks per cloud (max)
-  uint32_t* chunk_cnt; // [B][nchunk] (non-NaN count << 16) | NaN count
-  double* chunk_min;   // [B][nchunk] min non-NaN value of the chunk (+inf if none)
-  ndnet_ndt_stats* d_stats;  // [B] device copy of the stats
-  // k_front (ndt_front.h): the fused front of the pipeline
-  int front;                 // 1: k_front path, 0: the multi-kernel path
-  int front_ok;              // the plan's shape admits k_front
-  uint32_t fG, fbpw, frbs;   // workgroups per cloud, 1024-point bins per workgroup, points per rank bin
-  size_t flds;               // dynamic LDS bytes of k_front
-  unsigned long long* flims; // [B][fG][6]
-  uint32_t* frec;            // [B][kFrontPhases][fG][kRecWords]
-  uint32_t* fwgcnt;          // [B][fG][ndcap]
-  uint32_t* fbar;            // [B][kBarStride]
-  unsigned long long* fmarks; // [B][kFrontMarkStride]: k_front phase stamps of WG 0 + start/end of every WG (timing level 2)
-  int exact_counts;           // k_front counts every bisection grid (ndnet_ndt_set_exact_counts)
-  int wq_l64;                 // k_welford_q light form: 1 light64 (one ND per lane), 0 lane quads
-  int wq_form;                // 0 auto (quads at CU share 1, light64 above), 1 light64, 2 quads
-  uint32_t wq_grid;           // k_welford_q workgroups: one per CU (of the plan's CU share)
-  int cus;                    // the device's CUs
-  int cu_share;               // k_front / k_welford_q use CUs / cu_share (ndnet_ndt_set_cu_share)
-  uint32_t* wq_ctr;           // [8][16] k_welford_q dynamic item counters, one per XCD (re-armed by k_kl_rank_chunks)
-  int eager_list;             // build every cloud's retained list in the run (ndnet_ndt_set_lazy_list(plan, 0))
-  int kl_fuse;                // the run's prune rides on the merge launch (kl_fusable; NDNET_KL_FUSE=0: k_kl)
-  int list_sort;              // 2 (auto): k_kl_sort at a CU share > 1 where the list fits (sort_fits); 1: wherever it fits;
-                              // 3: as 1 in k_kl_rank_sort's one launch; 0: k_kl_merge (NDNET_KL_SORT)
-  uint64_t front_sync_ticks;  // k_front's cloud-barrier timeout (ndnet_ndt_debug_set_sync_timeout)
-  int lists_built;            // the deferred lists of the last run are built (no further build launches)
-  int front_staged;           // k_front's scatter through LDS records (ndnet_ndt_set_front_staged; default 1)
-  int run_part;               // ndnet_ndt_set_run_part: 0 whole run, 1 front only, 2 from k_welford_q on
-  int lane_rec;               // this run's k_front still to be recorded on its lanes (front_lanes_finish)
-  int lane_g;                 // this plan's share of FrontLaneSet::gsum (G - 1)
-  uint32_t* heavy;            // [B][ndcap] the heavy NDs of each cloud (CloudCtl::heavy_n of them)
-  double* rtab;               // [n + 1][2] (rc, rl) per count for wq_heavy's divisions
-  uint32_t* lu_done;          // [B][ceil(ndcap / 64)] k_welford_q's per-group completion counters (re-armed to 0)
-  uint32_t heavy_t;           // NDs with >= heavy_t samples take wq_heavy (ndnet_ndt_set_heavy_threshold)
-  // k_front admission (front_gate): the device's front lanes this plan's
-  // k_front occupies, and the barrier-timeout flag k_front raises in host memory
-  int dev;                    // the device the plan lives on
-  int lane0, nlanes;          // lanes [lane0, lane0 + nlanes) mod kFrontLanes
-  hipEvent_t front_ev;        // records this plan's k_front launches (the lanes' admission)
-  uint32_t* sync_fail_h;      // pinned host word (mapped): nonzero after a k_front barrier timeout
-  uint32_t* sync_fail_d;      // its device address
-};
-
-// ------------------------------------------------------------------ helpers
-
-__device__ inline uint32_t hash32(uint32_t k) { return (k * 2654435761u) >> (32 - 11); }
-
-template <typename T>
-__device__ inline void load_point(const T* pts, uint64_t i, double* x) {
-  x[0] = (double)pts[3 * i + 0];
-  x[1] = (double)pts[3 * i + 1];
-  x[2] = (double)pts[3 * i + 2];
-}
-
-// Inclusive wave scan (64 lanes) with op; returns inclusive value.
-template <typename T, typename Op>
-__device__ inline T wave_incl_scan(T x, Op op) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    T y = __shfl_up(x, o, 64);
-    if (lane >= o) x = op(y, x);
-  }
-  return x;
-}
-
-// Exclusive block scan of one value per thread.  `scratch` holds >= 16 T.
-template <typename T, typename Op>
-__device__ inline T block_excl_scan(T v, T identity, Op op, T* scratch, T& total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  T incl = wave_incl_scan(v, op);
-  T excl_w = __shfl_up(incl, 1, 64);
-  if (lane == 0) excl_w = identity;
-  if (lane == 63) scratch[wid] = incl;
-  __syncthreads();
-  if (wid == 0) {
-    T s = lane < nw ? scratch[lane] : identity;
-    s = wave_incl_scan(s, op);
-    if (lane < nw) scratch[lane] = s;
-  }
-  __syncthreads();
-  T pre = wid > 0 ? scratch[wid - 1] : identity;
-  total = scratch[nw - 1];
-  __syncthreads();
-  return op(pre, excl_w);
-}
-
-// Exclusive block scan over ITEMS consecutive elements per thread (one
-// barrier round for blockDim * ITEMS elements).  v[j] becomes the exclusive
-// prefix of element j within the round; total is the round's reduction.
-template <int ITEMS, typename T, typename Op>
-__device__ inline void block_scan_items(T (&v)[ITEMS], T identity, Op op, T* scratch, T& total) {
-  T local = identity;
-#pragma unroll
-  for (int j = 0; j < ITEMS; j++) {
-    const T x = v[j];
-    v[j] = local;
-    local = op(local, x);
-  }
-  const T ex = block_excl_scan(local, identity, op, scratch, total);
-#pragma unroll
-  for (int j = 0; j < ITEMS; j++) v[j] = op(ex, v[j]);
-}
-
-struct AddU64 {
-  __device__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a + b; }
-};
-
-struct AddU32 {
-  __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
-};
-struct MinF64 {
-  __device__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
-
-__device__ inline void grid_from(const CloudCtl& c, double vs, uint32_t* len, double* off, uint64_t* V) {
-  // voxel.c:61-81: len = (int)ceil(dim / vs), offset = min
-  uint64_t v = 1;
-  for (int a = 0; a < 3; a++) {
-    const double d = c.lim[a] - c.lim[3 + a];
-    const double q = ceil(d / vs);
-    int li;
-    if (q >= -2147483648.0 && q < 2147483648.0) li = (int)q;
-    else li = (int)0x80000000;  // x86 cvttsd2si overflow value
-    len[a] = (uint32_t)li;
-    off[a] = c.lim[3 + a];
-    v *= (uint64_t)len[a];
-  }
-  *V = v;
-}
+#include "ndt_plan.h"
+#include "ndt_block.h"
 
 // ------------------------------------------------------------------ kernels
 
@@ -903,10 +677,11 @@ constexpr int kWqNB = 4;                     // register blocks in the prefetch 
 #ifndef NDNET_WQ_RT
 #define NDNET_WQ_RT 4096
 #endif
-#ifdef NDNET_WQ_WPE  // A/B: cap the registers (waves per SIMD) so other kernels' waves fit beside it
-#define NDNET_WQ_ATTR __attribute__((amdgpu_waves_per_eu(NDNET_WQ_WPE)))
-#else
-#define NDNET_WQ_ATTR
+// NDNET_WQ_WPC workgroups per CU in Plan::wq_grid (1, 2 and 3 measured equal
+// on C2 and C5: profiles/r02c_welford_parts.txt -- the kernel is issue-bound,
+// not latency-bound, so a second wave per SIMD shares the same issue slots)
+#ifndef NDNET_WQ_WPC
+#define NDNET_WQ_WPC 1
 #endif
 constexpr int kWqRt = NDNET_WQ_RT;           // reciprocals tabled in LDS at most (32 KB; larger counts compute theirs)
 // Entries of the table a run needs: the light quads' counts stay below the
@@ -914,9 +689,6 @@ constexpr int kWqRt = NDNET_WQ_RT;           // reciprocals tabled in LDS at mos
 // another stream's kernels can use beside k_welford_q (pipelined U +2 %,
 // profiles/r04_wq_lds.txt); counts past the table compute their reciprocal.
 __host__ __device__ inline uint32_t wq_rt_entries(uint32_t heavy_t) {
-#ifdef NDNET_WQ_RTFULL  // A/B: the whole table whatever the threshold (round 1-4 form)
-  return (uint32_t)kWqRt;
-#endif
   // + 32: a light64 group's last round reads the pairs of up to 3 x 8 counts past its longest ND
   return heavy_t + 32u < (uint32_t)kWqRt ? (heavy_t + 32u + 31u) & ~31u : (uint32_t)kWqRt;
 }
@@ -930,9 +702,6 @@ constexpr int kWqHistMax = 64 * 1024;        // LDS class histograms up to this 
 // blocks, 128 samples in flight -- the per-coordinate loads were capped by the
 // 63 outstanding loads a wave can count) gained 1 us more on L but lost 2 on
 // C2 and 3 on C5 (longer masked tails).
-#ifndef NDNET_WQ_VLOAD
-#define NDNET_WQ_VLOAD 1
-#endif
 constexpr int kWqStageQ = 100;               // LDS words per quad stage (96 + pad: conflict-free reads)
 template <typename T, bool kVec, int kU>
 struct WqBlk { T v[kU]; };                       // coordinate j of samples q0 .. q0 + kU - 1 (lane j)
@@ -1116,19 +885,12 @@ __device__ inline void hv_block(double& m, double& acc, const double* __restrict
 // The full-block loop with its memory operations as inline asm, so that
 // their order and waits are exactly this: per group G of 8 steps, one
 // s_waitcnt lgkmcnt(0) covers its operands (issued a group earlier: four
-// ds_read_b128 of the lane's row, two s_load_dwordx16 of the (rc, rl) table)
-// and the mean writes of group G - 2; then the means of group G - 1 are
-// written and group G + 1's operands issued before group G's steps.  (With
-// compiler-placed loads the scalar loads, which return out of order, made
-// every wait an lgkmcnt(0) right at the use.)  The wait's in-out operands
-// keep every use of the loaded registers behind it.
-typedef unsigned int hv_u16 __attribute__((ext_vector_type(16)));
+// ds_read_b128 of the lane's row, eight of the block's (rc, rl) row) and the
+// mean writes of group G - 2; then the means of group G - 1 are written and
+// group G + 1's operands issued before group G's steps.  The wait's in-out
+// operands keep every use of the loaded registers behind it.
 typedef double hv_d2 __attribute__((ext_vector_type(2)));  // native vector (HIP's double2 is a struct)
 
-#ifndef NDNET_WQ_HV_RLDS
-#define NDNET_WQ_HV_RLDS 1
-#endif
-#if NDNET_WQ_HV_RLDS
 // (rc, rl) of the 8 steps from the block's LDS row (every lane the same
 // address: a broadcast), written in phase 0 from the (rc, rl) each lane
 // loaded for its own sample three blocks ahead (HvRec::r) -- no scalar loads,
@@ -1153,41 +915,6 @@ __device__ inline void hv_wait(HvOps& o) {
                : "+v"(o.x[0]), "+v"(o.x[1]), "+v"(o.x[2]), "+v"(o.x[3]), "+v"(o.r[0]), "+v"(o.r[1]), "+v"(o.r[2]),
                  "+v"(o.r[3]), "+v"(o.r[4]), "+v"(o.r[5]), "+v"(o.r[6]), "+v"(o.r[7]));
 }
-#else
-struct HvOps {
-  hv_d2 x[4];  // 8 steps' coordinates (lanes 0..2) or addends (lanes 3..8)
-  hv_u16 r0, r1;  // (rc, rl) of the 8 steps, in scalar registers
-};
-
-template <int G>
-__device__ inline void hv_issue(HvOps& o, uint32_t rda, const double2* rtq) {
-  hv_d2 x0, x1, x2, x3;
-  hv_u16 r0, r1;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x0) : "v"(rda), "n"(64 * G));
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x1) : "v"(rda), "n"(64 * G + 16));
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x2) : "v"(rda), "n"(64 * G + 32));
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x3) : "v"(rda), "n"(64 * G + 48));
-  asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(r0) : "s"(rtq), "n"(128 * G));
-  asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(r1) : "s"(rtq), "n"(128 * G + 64));
-  o.x[0] = x0;
-  o.x[1] = x1;
-  o.x[2] = x2;
-  o.x[3] = x3;
-  o.r0 = r0;
-  o.r1 = r1;
-}
-__device__ inline void hv_wait(HvOps& o) {
-  hv_d2 x0 = o.x[0], x1 = o.x[1], x2 = o.x[2], x3 = o.x[3];
-  hv_u16 r0 = o.r0, r1 = o.r1;
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+s"(r0), "+s"(r1));
-  o.x[0] = x0;
-  o.x[1] = x1;
-  o.x[2] = x2;
-  o.x[3] = x3;
-  o.r0 = r0;
-  o.r1 = r1;
-}
-#endif
 template <int G>
 __device__ inline void hv_put(uint32_t wra, const double (&mo)[8]) {
   const hv_d2 a = {mo[0], mo[1]}, b = {mo[2], mo[3]}, c = {mo[4], mo[5]}, d = {mo[6], mo[7]};
@@ -1196,30 +923,18 @@ __device__ inline void hv_put(uint32_t wra, const double (&mo)[8]) {
   asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(wra), "v"(c), "n"(64 * G + 32));
   asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(wra), "v"(d), "n"(64 * G + 48));
 }
-__device__ inline double hv_sd(const hv_u16& v, int k) {
-  return __builtin_bit_cast(double, (unsigned long long)v[2 * k] | ((unsigned long long)v[2 * k + 1] << 32));
-}
 __device__ inline void hv_steps(double& m, double& acc, const HvOps& o, double (&mo)[8]) {
 #pragma unroll
   for (int u = 0; u < 8; u++) {
     const double xv = o.x[u >> 1][u & 1];
-#if NDNET_WQ_HV_RLDS
     const double rc = o.r[u][0], rl = o.r[u][1];
-#else
-    const hv_u16& r = u < 4 ? o.r0 : o.r1;
-    const double rc = hv_sd(r, 2 * (u & 3)), rl = hv_sd(r, 2 * (u & 3) + 1);
-#endif
     const double t = xv - m;
     m = m + fma(t, rc, t * rl);
     acc = acc + xv;
     mo[u] = m;
   }
 }
-#if NDNET_WQ_HV_RLDS
 typedef uint32_t HvRt;  // LDS byte address of the block's (rc, rl) row
-#else
-typedef const double2* HvRt;  // the block's first (rc, rl) in the global table
-#endif
 template <int G>  // group G of a full block: wait for its operands, write G - 1's means, issue G + 1's operands, step
 __device__ inline void hv_group(double& m, double& acc, HvOps& cur, HvOps& nxt, double (&mcur)[8],
                                 double (&mprev)[8], uint32_t rda, uint32_t wra, HvRt rtq) {
@@ -1231,12 +946,7 @@ __device__ inline void hv_group(double& m, double& acc, HvOps& cur, HvOps& nxt, 
   // after this group's steps, right before their wait (the LDS latency
   // exposed once per group).  m and acc pass through an asm statement placed
   // after the reads, so the steps start only once they are issued.
-#ifndef NDNET_WQ_HV_ORDER
-#define NDNET_WQ_HV_ORDER 1
-#endif
-#if NDNET_WQ_HV_ORDER
   asm volatile("" : "+v"(m), "+v"(acc));
-#endif
   hv_steps(m, acc, cur, mcur);
 }
 __device__ inline void hv_block_asm(double& m, double& acc, uint32_t rda, uint32_t wra, HvRt rtq) {
@@ -1300,9 +1010,7 @@ __device__ inline void wq_heavy(const T* __restrict__ rec, uint32_t cnt, const d
     X[kHvS + lane] = x1;
     X[2 * kHvS + lane] = x2;
     if (lane < 3) M[a * kHvS + 1] = m;
-#if NDNET_WQ_HV_RLDS
     hr[lane] = h.r;  // the block's (rc, rl) row for the loop's broadcast reads
-#endif
     asm volatile("" ::: "memory");  // one wave's LDS operations complete in order
     stamp(c0);
     // 1. the recurrence (lanes 0..2) + the previous block's ordered sums (lanes 3..8)
@@ -1310,13 +1018,7 @@ __device__ inline void wq_heavy(const T* __restrict__ rec, uint32_t cnt, const d
       if (nb == 64)
         hv_block_asm(m, acc, (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const double*)rd,
                      (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)wr,
-#if NDNET_WQ_HV_RLDS
                      (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double2*)hr);
-#elif defined(NDNET_WQ_HV_FIXRT)  // timing experiment only (wrong results): every block reads block 0's (rc, rl)
-                     rtab + 1);
-#else
-                     rtab + q0 + 1);
-#endif
       else
         hv_block<true>(m, acc, rd, wr, rtab, q0, nb);
     }
@@ -1491,9 +1193,6 @@ __global__ void __launch_bounds__(64) k_debug_lu_chain(const double* A, uint32_t
 constexpr uint32_t wq_light_nds(bool l64) { return l64 ? 64u : 16u; }  // NDs per light item (one wave)
 constexpr int kL64B = 8;                                      // samples per register block
 static_assert(4 * kL64B <= 32, "wq_rt_entries' margin covers a light64 group's last round (ring <= 4)");
-#ifndef NDNET_WQ_L64_COALESCE
-#define NDNET_WQ_L64_COALESCE 1
-#endif
 constexpr size_t wq_rt_bytes(bool l64) { return l64 ? sizeof(double2) : sizeof(double); }  // LDS table entry
 constexpr uint32_t wq_hist_nds(bool l64) { return l64 ? kWqThreads : kWqNDs; }          // NDs of a workgroup at once
 
@@ -1662,7 +1361,7 @@ __device__ __attribute__((always_inline)) inline void wq_light64(const CloudCtl*
     }
   };
   // a ring of register blocks: kR - 1 blocks in flight while one is folded
-  constexpr bool kCo = std::is_same<T, float>::value && NDNET_WQ_L64_COALESCE;  // coalesced loads + LDS transpose
+  constexpr bool kCo = std::is_same<T, float>::value;  // float input: coalesced loads + LDS transpose
 #ifndef NDNET_WQ_L64_RING
 #define NDNET_WQ_L64_RING 3
 #endif
@@ -1896,7 +1595,7 @@ __device__ __attribute__((always_inline)) inline void wq_light64(const CloudCtl*
 }
 
 template <typename T, bool L64>
-__global__ void __launch_bounds__(kWqThreads) NDNET_WQ_ATTR k_welford_q(const CloudCtl* ctl, int B, const T* __restrict__ nd_pts,
+__global__ void __launch_bounds__(kWqThreads) k_welford_q(const CloudCtl* ctl, int B, const T* __restrict__ nd_pts,
                                                           const uint16_t* __restrict__ nd_lbl,
                                                           const uint32_t* __restrict__ nd_n,
                                                           const uint32_t* __restrict__ nd_base, double* nd_mean,
@@ -1977,14 +1676,7 @@ __global__ void __launch_bounds__(kWqThreads) NDNET_WQ_ATTR k_welford_q(const Cl
     return __builtin_amdgcn_readfirstlane(v);
   };
   for (uint32_t item = blockIdx.x * (kWqThreads / 64) + wave; item < total; item = next_item()) {
-#ifdef NDNET_WQ_EXP_LIGHTONLY  // register probe only (wrong results): the light path alone
-  const bool hv = false;
-#else
   const bool hv = item < H;  // a heavy ND (wave-uniform)
-#endif
-#ifdef NDNET_WQ_EXP_HEAVYONLY  // timing experiment only (wrong results): light items skipped
-  if (!hv) continue;
-#endif
   unsigned long long mk_rt = 0, mk_t0 = 0, mk_t1 = 0;
   if (wq_marks) {
     mk_rt = __builtin_amdgcn_s_memrealtime();
@@ -2034,7 +1726,7 @@ __global__ void __launch_bounds__(kWqThreads) NDNET_WQ_ATTR k_welford_q(const Cl
   const uint32_t last = cnt ? cnt - 1u : 0u;
   const uint32_t jj = j < 3 ? j : 0u;
   const T* src = nd_pts + ((uint64_t)b * n + beg) * 3 + jj;
-  constexpr bool kVec = NDNET_WQ_VLOAD && std::is_same<T, float>::value;
+  constexpr bool kVec = std::is_same<T, float>::value;
 #ifndef NDNET_WQ_VU
 #define NDNET_WQ_VU 1
 #endif
@@ -2082,24 +1774,14 @@ __global__ void __launch_bounds__(kWqThreads) NDNET_WQ_ATTR k_welford_q(const Cl
 #pragma unroll
       for (int i = 0; i < kU / 4; i++) {
         const uint32_t q = q0 + (uint32_t)(kU / 4) * j + (uint32_t)i;
-#ifdef NDNET_WQ_NOLOAD  // timing experiment only: no point loads (wrong results)
-        r.v[i] = make_float3(1.0f + 0.001f * (float)(q & 7), 2.0f, 3.0f);
-#else
         const float* pq = rec + 3u * (q < last ? q : last);
         r.v[i] = make_float3(pq[0], pq[1], pq[2]);
-#endif
       }
     } else {
 #pragma unroll
       for (int u = 0; u < kU; u++) {
         const uint32_t q = q0 + (uint32_t)u;
-#ifdef NDNET_WQ_NOLOAD  // timing experiment only: no point loads (wrong results)
-        r.v[u] = (T)(1.0f + 0.001f * (float)(q & 7));
-#elif defined(NDNET_WQ_HOTLOAD)  // timing experiment only: loads of a few cached lines (wrong results)
-        r.v[u] = nd_pts[jj + 3u * (q & 7u)];
-#else
         r.v[u] = src[3u * (q < last ? q : last)];
-#endif
       }
     }
   };
@@ -2149,13 +1831,7 @@ __global__ void __launch_bounds__(kWqThreads) NDNET_WQ_ATTR k_welford_q(const Cl
       for (int u = 0; u < kU; u++) r[u] = rb.v[u];
     }
     double cr[kU];
-#ifdef NDNET_WQ_NORECIP  // timing experiment only (wrong results): reciprocals without their LDS reads
-    if constexpr (!kExact)
-#pragma unroll
-      for (int u = 0; u < kU; u++) cr[u] = 1.0 / 3.0 + u;
-#else
     if constexpr (!kExact) recips(cr, q0);
-#endif
     double pt = 0.0, pu = 0.0, pcn = 1.0, prc = 1.0;       // the previous sample's head results
     unsigned long long plane = 0;
     if constexpr (kExact) {
@@ -2423,7 +2099,13 @@ __global__ void __launch_bounds__(kWqThreads) NDNET_WQ_ATTR k_welford_q(const Cl
   }  // item
 }
 
-// Bitonic sort of (key, idx) pairs ascending, n a power of two, within one workgroup.
+// ------------------------------------------------------------------ the KL stage
+// Dynamic LDS a KL kernel may be launched with (k_kl, k_kl_sort, k_kl_rank_sort, k_prune)
+constexpr int kKLLdsMax = 150 * 1024;
+// The dynamic LDS of the fused merge + prune launches (k_kl_merge<.., true>):
+// the larger of the merge's and the LDS-resident prune's (kl_lds_bytes).
+constexpr size_t kKLFusedLds = kMergeScoreChunks * kChunk * sizeof(unsigned long long);  // 144 KB
+
 // phase stamp of k_kl (timing level 2): 100 MHz constant clock
 #define KL_MARK(i)                                                                   \
   do {                                                                               \
@@ -2999,11 +2681,7 @@ __global__ void __launch_bounds__(kChunk) k_kl_rank_chunks(KLArgs A) {
   if (deferred) {
     fl = kl_event_flag(A, b, sl < nslots ? sl : 0u);
   } else {
-#ifdef NDNET_RANK_NOSCORE  // timing experiment only (wrong results): flags without the KL scores
-    kl_event(A, b, sl < nslots ? sl : 0u, false, fl, vl);
-#else
     kl_event(A, b, sl < nslots ? sl : 0u, true, fl, vl);  // the clamped slot's result is dropped
-#endif
   }
   if (deferred) {  // count the cloud's events (stats num_events / num_kl), one atomic per wave
     const unsigned long long bal = __ballot(sl < nslots && fl);
@@ -3043,9 +2721,6 @@ __global__ void __launch_bounds__(kChunk) k_kl_rank_chunks(KLArgs A) {
   // Non-score slots (key ~0) go after the chunk's scores in slot order: only
   // the scores' positions are read (k_kl_merge), the rest must only be ~0.
   uint32_t lt = 0, eq = 0;
-#ifdef NDNET_RANK_NORANK  // timing experiment only (wrong results): no in-chunk rank count
-  if (false)
-#endif
 #pragma unroll 4
   for (uint32_t j = 0; j < nnum; j += 2) {
     const ulonglong2 kk = *reinterpret_cast<const ulonglong2*>(&s_nkey[j]);
@@ -3578,6 +3253,12 @@ __global__ void __launch_bounds__(kChunk * kMergeRuns) k_kl_merge(KLArgs A) {
 // searches (~250), and the launch holds 16 CUs instead of the merge's ~110-224:
 // the L line's KL stage is CU time the chains share.
 constexpr uint32_t kSortMaxChunks = 64;          // the offsets are one wave's scan
+constexpr int kSortSlotBytes = 20;               // LDS per slot: 64-bit key + 16-bit slot, in two buffers
+// rounds of kKLThreads slots that sort_cloud stages in registers before it places them
+constexpr int kSortRegRounds = (kSortMaxChunks * kChunk / 2 + kKLThreads - 1) / kKLThreads;
+// the largest ecap sort_fits admits, rounded up to whole chunks: the slots sort_cloud loads
+constexpr int kSortMaxSlots = (kKLLdsMax / kSortSlotBytes + kChunk - 1) / kChunk * kChunk;
+static_assert(kSortRegRounds * kKLThreads >= kSortMaxSlots, "sort_cloud's register staging covers every slot it loads");
 static_assert(kKLThreads == 1024, "k_kl_sort's item loops assume 1024 threads");
 
 // One buffer of the sort: the 64-bit keys and the slots.
@@ -3748,7 +3429,7 @@ __device__ void sort_cloud(const KLArgs& A, const int b) {
   __shared__ uint32_t s_maxrun[8];
   // every slot of the chunks' runs and NaN lists loaded in one round (the
   // counts arrive with them), placed once the offsets are known
-  constexpr int U = (kSortMaxChunks * kChunk / 2 + kKLThreads - 1) / kKLThreads;  // 7680 slots at most: 8 rounds
+  constexpr int U = kSortRegRounds;  // 7680 slots at most: 8 rounds
   const uint32_t nslot = nch * kChunk;
   unsigned long long key[U];
   uint32_t sidx[U], nsl[U];
@@ -4006,22 +3687,7 @@ __global__ void __launch_bounds__(kKLThreads) k_kl_rank_sort(KLArgs A) {
   }
 }
 
-__global__ void __launch_bounds__(kKLThreads) k_prune(KLArgs A) {
-  const int b = blockIdx.x;
-  CloudCtl& c = A.ctl[b];
-  __shared__ uint32_t s_u32[16];
-  if (c.state != kAccepted) {
-    zero_outputs(A, b, A.k);
-    pad_class_rows(A, b, A.k, 0);
-    if (threadIdx.x == 0) write_stats(A, b);
-    return;
-  }
-  const uint32_t nout = A.kl_lds ? prune_and_emit<true>(A, b, A.k, s_u32, s_u32)
-                                 : prune_and_emit<false>(A, b, A.k, s_u32, s_u32);
-  fill_tail(A, b, A.k, nout < A.k ? nout : (uint32_t)A.k);
-  __syncthreads();
-  if (threadIdx.x == 0) write_stats(A, b);
-}
+#include "ndt_prune.h"
 
 // ------------------------------------------------------------------ host side
 
@@ -4067,7 +3733,6 @@ static void plan_free(Plan* P) {
   delete P;
 }
 
-constexpr int kKLLdsMax = 150 * 1024;
 // dynamic LDS of k_kl / k_prune's LDS-resident prune (prune_and_emit<true>)
 static size_t kl_lds_bytes(const Plan* P) {
   return 4 * ((size_t)P->ndcap + 2 * (size_t)P->ecap) + ((P->ndcap + 3) & ~3u);
@@ -4133,57 +3798,18 @@ static KLArgs kl_args(Plan* P, uint64_t k, float* out, float* out_cls, double* p
 
 static size_t merge_lds_bytes(const Plan* P);
 
-// The event sort of the clouds in A's scope (every cloud in a run, the
-// deferred ones in a build).
-// The LU chain states of a deferred cloud (k_welford_q stored only their
-// determinant bits): from the pre-KL covariance and the chain mask, the same
-// in-place lu3 sequence as k_welford_q's epilogue, one thread per ND.
-__global__ void __launch_bounds__(256) k_kl_chains(KLArgs A) {
-  const int b = blockIdx.y;
-  const CloudCtl& c = A.ctl[b];
-  if (c.state != kAccepted || !c.kl_deferred) return;
-  const uint32_t u = blockIdx.x * 256 + threadIdx.x;
-  if (u >= c.num_nds) return;
-  const uint64_t ob = (uint64_t)b * A.ndcap;
-  double S[9];
-#pragma unroll
-  for (int q = 0; q < 9; q++) S[q] = A.nd_cov[9 * (ob + u) + q];
-  const int nT = __popc(A.nkeys_all[ob + u]);
-  double* chain = A.chain_all + ob * 108 + u;
-  uint32_t* ps = A.chain_ps_all + ob * 12 + u;
-  for (int t = 0; t < nT; t++) {
-    uint32_t perm;
-    int sg;
-    lu3(S, perm, sg);
-#pragma unroll
-    for (int q = 0; q < 9; q++) chain[(uint64_t)(9 * t + q) * A.ndcap] = S[q];
-    ps[(uint64_t)t * A.ndcap] = perm | (sg < 0 ? 0x100u : 0u);
-  }
-}
-
-// The dynamic LDS of the fused merge + prune launches (k_kl_merge<.., true>):
-// the larger of the merge's and the LDS-resident prune's (kl_lds_bytes).
-constexpr size_t kKLFusedLds = kMergeScoreChunks * kChunk * sizeof(unsigned long long);  // 144 KB
-static size_t kl_lds_bytes(const Plan* P);
-
 // Merge workgroups per cloud for chunk groups of `runs` chunks: one per group,
 // or at a CU share s > 1 (a pipeline's plan) 1 / s of that, each workgroup
 // taking several groups after one staging of the runs: the merge's workgroups
 // hold a CU each (110 KB of LDS at C2-L) and no chain workgroup fits beside
-// them, so a pipeline trades the merge's latency for its CU footprint.
-// NDNET_MERGE_SHARE (A/B, read once): 1 = one workgroup per group always.
+// them, so a pipeline trades the merge's latency for its CU footprint
+// (profiles/r06o_merge_grid_ab.txt).
 static uint32_t merge_grid(const Plan* P, uint32_t runs) {
-  static const int env = [] {
-    const char* e = getenv("NDNET_MERGE_SHARE");
-    return e ? atoi(e) : 0;
-  }();
   const uint32_t groups = (P->nchunk + runs - 1) / runs;
-  const uint32_t share = env > 0 ? (uint32_t)env : (P->cu_share > 1 ? (uint32_t)P->cu_share : 1u);
+  const uint32_t share = P->cu_share > 1 ? (uint32_t)P->cu_share : 1u;
   return (groups + share - 1) / share;
 }
 
-// tail: the merge's last workgroup per cloud also prunes and emits the rows
-// (k_kl's work; the caller checked kl_fusable).
 // k_kl_sort takes the list when its two key/slot buffers (20 bytes per slot)
 // fit its LDS and its offsets one wave's scan (ecap <= 7680: k <= 1065), and
 // by default only for a plan with a CU share (a pipeline's): one workgroup per
@@ -4192,12 +3818,17 @@ static uint32_t merge_grid(const Plan* P, uint32_t runs) {
 // the chip keeps the merge, while a pipeline gains the merge's CU time (its
 // 110 KB workgroups hold ~110 CUs): the L line 66.2 / 66.6k vs 65.2 / 64.8k
 // clouds/s (profiles/r06z_list_sort_ab.txt)
-static size_t sort_lds_bytes(const Plan* P) { return 20 * (size_t)P->ecap; }
+static size_t sort_lds_bytes(const Plan* P) { return kSortSlotBytes * (size_t)P->ecap; }
 static bool sort_fits(const Plan* P) {
   const bool want = P->list_sort == 1 || P->list_sort == 3 || (P->list_sort == 2 && P->cu_share > 1);
   return want && sort_lds_bytes(P) <= (size_t)kKLLdsMax && P->nchunk <= kSortMaxChunks && P->ecap <= 65536;
 }
 
+// The event sort of the clouds in A's scope (every cloud in a run, the
+// deferred ones in a build).
+//
+// tail: the merge's last workgroup per cloud also prunes and emits the rows
+// (k_kl's work; the caller checked kl_fusable).
 static void launch_list_sort(Plan* P, const KLArgs& A, hipStream_t st, bool tail = false) {
   const int B = P->B;
   if (sort_fits(P)) {
@@ -4262,253 +3893,7 @@ static int build_deferred_lists(Plan* P, hipStream_t st) {
 
 static size_t merge_lds_bytes(const Plan* P) { return 2 * (size_t)P->nchunk * kChunk * sizeof(unsigned long long); }
 
-// ---- k_front admission: the device's front lanes ----
-//
-// k_front's workgroups of a cloud meet at cloud barriers, so all of them must
-// be resident at once.  Two k_front grids that together want more workgroups
-// than the chip holds can each get part of their workgroups resident and then
-// wait on each other until the barrier timeout fails their clouds (measured:
-// 640 ms per step, profiles/r04_ndt_streams_guard.txt).  The library rules that
-// out itself, for any number of plans and streams, eager or captured in HIP
-// graphs: the chip is split into kFrontLanes lanes of CUs / kFrontLanes; a
-// plan's k_front occupies ceil(kFrontLanes * workgroups / CUs) of them (all four
-// at CU share 1, two at share 2); before its launch the stream waits for the
-// last k_front launched on each of its lanes, and after it the launch is
-// recorded in the plan's own event, which becomes those lanes' last launch
-// (explicit event graph nodes when the stream is being captured, so a replayed
-// graph waits for the k_front launches before it, whatever stream they ran
-// on).  A wait is left out when stream order already gives it (the lane's last
-// launch came from the same stream in the same capture, or both eager), and
-// lanes whose last launch shares an event are waited on once (round-5 r05e:
-// four waits + four records per run cost 19 us of k_front stage).  So the
-// k_front launches in flight at any time never want more workgroups than
-// there are CUs, and grids on disjoint lanes (two share-2 plans: the
-// pipeline's NDT streams) still run concurrently.  The other kernels never
-// wait on anything, so they drain.
-//
-// Round 6: the admission is engaged only where it is needed.  k_front deals a
-// launch's clouds cloud-major within each XCD (ndt_front.h), so a launch
-// leaves at most G - 1 workgroups of one partially resident cloud waiting on
-// an XCD.  While the live path-2 plans of the device together have
-// sum (G - 1) < CUs per XCD (32), every XCD always keeps a CU free or a cloud
-// completing, whatever the plans' launches overlap: no barrier can wait on a
-// workgroup that never starts, and no admission is needed.  That covers one or
-// two share-1 plans (15 + 15), and up to four share-2 plans (7 each).  Past
-// the bound the lanes order the launches as above.  The bound matters: an
-// event node in a replayed graph costs ~6 us (C2 alone: 151k clouds/s with
-// the lanes' record and wait nodes, 171k without: profiles/r06d_lanes_ab.txt).
-constexpr int kFrontLanes = 4;
-constexpr int kMaxDevices = 64;
-struct FrontLaneSet {
-  int next;                          // the lane the next plan's lanes start at (round robin)
-  int plans;                         // live plans holding a lane event on this device
-  int gsum;                          // sum over them of (G - 1): their partial workgroups per XCD at most
-  hipEvent_t ev[kFrontLanes];        // the event of the lane's last k_front launch (null: none yet)
-  hipStream_t st[kFrontLanes];       // the stream it was launched on
-  unsigned long long cap[kFrontLanes];  // the capture it was launched in (0: eager)
-  std::vector<hipEvent_t> pool;      // events of freed plans, reused by later plans
-};
-static FrontLaneSet g_lanes[kMaxDevices];
-
-// Drops a freed plan's event from the lanes (caller holds g_lane_mu; the
-// event has completed, so nothing left to wait for).  The event itself is
-// kept in the device's pool and handed to the next plan: a graph captured
-// while this plan held a lane may still hold a wait node on it,
-// and waiting on a pooled event only ever waits for a completed or a later
-// k_front launch.
-static void front_lanes_forget(Plan* P) {
-  if (P->dev < 0 || P->dev >= kMaxDevices || !P->front_ev) return;
-  FrontLaneSet& L = g_lanes[P->dev];
-  for (int i = 0; i < kFrontLanes; i++)
-    if (L.ev[i] == P->front_ev) L.ev[i] = nullptr;
-  L.pool.push_back(P->front_ev);
-  L.plans--;
-  L.gsum -= P->lane_g;
-  P->lane_g = 0;
-  P->front_ev = nullptr;
-}
-
-// Assigns the plan's lanes for its current k_front geometry (caller holds g_lane_mu).
-static hipError_t front_lanes_assign(Plan* P) {
-  if (P->dev < 0 || P->dev >= kMaxDevices) return hipErrorInvalidDevice;
-  FrontLaneSet& L = g_lanes[P->dev];
-  if (!P->front_ev) {
-    if (!L.pool.empty()) {
-      P->front_ev = L.pool.back();
-      L.pool.pop_back();
-    } else {
-      const hipError_t e = hipEventCreateWithFlags(&P->front_ev, hipEventDisableTiming);
-      if (e != hipSuccess) return e;
-    }
-    L.plans++;
-  }
-  L.gsum -= P->lane_g;
-  P->lane_g = P->fG > 1 ? (int)P->fG - 1 : 0;
-  L.gsum += P->lane_g;
-  const uint64_t wgs = (uint64_t)P->fG * (uint64_t)P->B;
-  const int cus = P->cus > 0 ? P->cus : 1;
-  int nl = (int)((wgs * kFrontLanes + (uint64_t)cus - 1) / (uint64_t)cus);
-  nl = nl < 1 ? 1 : nl > kFrontLanes ? kFrontLanes : nl;
-  P->nlanes = nl;
-  P->lane0 = L.next;
-  L.next = (L.next + nl) % kFrontLanes;
-  return hipSuccess;
-}
-
-// Launches k_front between the lane waits and records (front_lanes_assign).
-// A stream being captured is admitted with explicit graph nodes
-// (hipGraphAddEventWaitNode / hipGraphAddEventRecordNode on the capture's
-// graph, then the capture's dependencies moved past them).  The capture forms
-// hipStreamWaitEvent(hipEventWaitExternal) and
-// hipEventRecordWithFlags(hipEventRecordExternal) abort inside HIP on ROCm 7.2
-// (std::bad_alloc; error -21: profiles/r05_capture_lane_probe.txt) and are not
-// used.  NDNET_LANE_CAPTURE=0 (A/B only, read once) puts no lane nodes in a
-// captured graph.
-static bool lane_capture_nodes() {
-  static const bool v = [] {
-    const char* e = getenv("NDNET_LANE_CAPTURE");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// Whether the device's live plans need the admission (the bound above);
-// NDNET_FRONT_ADMIT=1 (A/B, tests) engages it always.  A launch made while
-// the bound held records nothing; when more plans make it fail, their
-// launches and the earlier ones' last runs may overlap once: the earlier plans
-// alone were within the bound, and the lanes order everything after.
-static bool admit_always() {
-  static const bool v = [] {
-    const char* e = getenv("NDNET_FRONT_ADMIT");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-static bool admission_needed(const Plan* P, const FrontLaneSet& L) {
-  const int per_xcd = P->cus >= 8 ? P->cus / 8 : 1;
-  return admit_always() || L.gsum >= per_xcd;
-}
-
-// Adds an event node (wait or record) after the capture's current
-// dependencies and makes it the capture's only dependency.
-static hipError_t capture_event_node(hipStream_t st, hipEvent_t ev, bool wait) {
-  hipStreamCaptureStatus cs;
-  unsigned long long id = 0;
-  hipGraph_t g = nullptr;
-  const hipGraphNode_t* deps = nullptr;
-  size_t nd = 0;
-  hipError_t e = hipStreamGetCaptureInfo_v2(st, &cs, &id, &g, &deps, &nd);
-  if (e != hipSuccess) return e;
-  std::vector<hipGraphNode_t> dv(deps, deps + nd);
-  hipGraphNode_t node;
-  e = wait ? hipGraphAddEventWaitNode(&node, g, dv.data(), dv.size(), ev)
-           : hipGraphAddEventRecordNode(&node, g, dv.data(), dv.size(), ev);
-  if (e != hipSuccess) return e;
-  return hipStreamUpdateCaptureDependencies(st, &node, 1, hipStreamSetCaptureDependencies);
-}
-
-// NDNET_FRONT_LANES=0 (A/B only, read once): no admission at all -- the round-4
-// behaviour, concurrent path-2 plans then need front_share >= N
-static bool lanes_enabled() {
-  static const bool v = [] {
-    const char* e = getenv("NDNET_FRONT_LANES");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// Where a plan's k_front is recorded on its lanes: at the end of its run (the
-// default: a record node between k_front and k_welford_q held the next launch
-// back -- the isolated C2 k_front stage 51 -> 55 us, profiles/r05_lanes_ab.txt;
-// at the run's end it follows the last KL launch, where the pipeline records
-// its own stage event anyway), or right after k_front (NDNET_FRONT_REC_END=0,
-// A/B).  A later k_front on those lanes then waits for the whole run instead
-// of its k_front only: stricter, and still one chip's worth at a time.
-static bool rec_at_end() {
-  static const bool v = [] {
-    const char* e = getenv("NDNET_FRONT_REC_END");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// Records the plan's last k_front launch on its lanes (caller holds g_lane_mu).
-static int front_lanes_record(Plan* P, hipStream_t st) {
-  FrontLaneSet& L = g_lanes[P->dev];
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  unsigned long long cap_id = 0;
-  HIPCHK(hipStreamGetCaptureInfo(st, &cs, &cap_id));
-  const bool cap = cs == hipStreamCaptureStatusActive;
-  if (!cap) cap_id = 0;
-  if (cap && !lane_capture_nodes()) return NDNET_OK;  // the lanes keep their last launch
-  if (!cap) HIPCHK(hipEventRecord(P->front_ev, st));
-  else HIPCHK(capture_event_node(st, P->front_ev, false));
-  for (int i = 0; i < P->nlanes; i++) {
-    const int l = (P->lane0 + i) % kFrontLanes;
-    L.ev[l] = P->front_ev;
-    L.st[l] = st;
-    L.cap[l] = cap_id;
-  }
-  return NDNET_OK;
-}
-
-// The record a run deferred to its end (rec_at_end): after its last launch.
-static int front_lanes_finish(Plan* P, hipStream_t st) {
-  if (!P->lane_rec) return NDNET_OK;
-  P->lane_rec = 0;
-  std::lock_guard<std::mutex> lk(g_lane_mu);
-  return front_lanes_record(P, st);
-}
-
-template <typename T>
-static void front_kernel(Plan* P, hipStream_t st, const T* pts, const FrontArgs& F) {
-  // grid, workgroups per cloud and LDS are the plan's, with or without counts
-  if (F.counts) k_front<T, true><<<P->fG * P->B, kFrontThreads, P->flds, st>>>(pts, F);
-  else k_front<T, false><<<P->fG * P->B, kFrontThreads, P->flds, st>>>(pts, F);
-}
-
-template <typename T>
-static int front_launch(Plan* P, hipStream_t st, const T* pts, const FrontArgs& F) {
-  P->lane_rec = 0;
-  if (!lanes_enabled()) {
-    front_kernel<T>(P, st, pts, F);
-    HIPCHK(hipGetLastError());
-    return NDNET_OK;
-  }
-  std::lock_guard<std::mutex> lk(g_lane_mu);  // waits and launch in one host order
-  FrontLaneSet& L = g_lanes[P->dev];
-  if (!admission_needed(P, L)) {
-    front_kernel<T>(P, st, pts, F);
-    HIPCHK(hipGetLastError());
-    return NDNET_OK;
-  }
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  unsigned long long cap_id = 0;
-  HIPCHK(hipStreamGetCaptureInfo(st, &cs, &cap_id));
-  const bool cap = cs == hipStreamCaptureStatusActive;
-  if (!cap) cap_id = 0;
-  const bool nodes = !cap || lane_capture_nodes();
-  hipEvent_t waited[kFrontLanes];
-  int nw = 0;
-  for (int i = 0; i < P->nlanes; i++) {
-    const int l = (P->lane0 + i) % kFrontLanes;
-    hipEvent_t ev = L.ev[l];
-    if (!ev || (L.st[l] == st && L.cap[l] == cap_id)) continue;  // nothing yet / stream order covers it
-    bool dup = false;
-    for (int j = 0; j < nw; j++) dup |= waited[j] == ev;
-    if (dup) continue;
-    waited[nw++] = ev;
-    if (!cap) HIPCHK(hipStreamWaitEvent(st, ev, 0));
-    else if (nodes) HIPCHK(capture_event_node(st, ev, true));
-  }
-  front_kernel<T>(P, st, pts, F);
-  HIPCHK(hipGetLastError());
-  if (rec_at_end()) {
-    P->lane_rec = 1;
-    return NDNET_OK;
-  }
-  return front_lanes_record(P, st);
-}
+#include "ndt_front_lanes.h"
 
 // k_welford_q's class-histogram LDS of a labelled run (0: the global histograms)
 static size_t wq_hist_lds(const Plan* P, bool l64) {
@@ -4636,227 +4021,11 @@ __global__ void k_set_epoch(CloudCtl* ctl, int B, uint32_t epoch) {
   if (b < B) ctl[b].epoch = epoch;
 }
 
-// ------------------------------------------------------- point -> output row
-//
-// k_point_rows: the output row every input point was folded into, after a run
-// (or a further prune level) of the plan.  A point contributed to an ND iff its
-// cloud has rc 0, it lies below the n % 8 tail and its worker's cut-off
-// (first_bad), and its key at the accepted grid -- voxel_key_f32 with
-// voxel_key as the fallback, from the constants k_front derives -- is in grid;
-// the ND is the dense id d with vox[d] == key (vox ascends: a binary search in
-// LDS), the row the number of alive NDs below d, where that is below
-// min(num_out, num_desired).  Every other point gets -1 or, with fill nearest,
-// the row whose fp32 mean is nearest (dx dx + dy dy + dz dz in fp32, the lowest
-// row on a tie); a point with a non-finite coordinate always gets -1.
-//
-// One workgroup per kPrPts points of a cloud: the points arrive as the flat
-// coalesced float stream (every load issued before the first use), vox and the
-// row table (a block scan of alive) are staged in LDS, the rows leave as
-// coalesced int32 stores.  The nearest phase gathers the workgroup's
-// unassigned points into an LDS list and searches them densely: a group of
-// L = 256 / (list length) lanes (a power of two, at most a wave) per point,
-// the rows dealt round-robin to the group's lanes, tiles of kPrTile row means
-// in LDS (over the vox / row-table region, dead by then).  Reads the plan's
-// state only.
-constexpr int kPrThreads = 256;
-constexpr int kPrPPT = 4;      // 1024 points per workgroup: 8 at 2048 measured 21.4 / 30.7 us (none / nearest, U)
-                               // against 18.2 / 21.5, 2 at 512 18.5 / 19.4 (profiles/point_labels.json's shape)
-constexpr int kPrPts = kPrThreads * kPrPPT;
-constexpr int kPrTile = 1024;  // row means per LDS tile of the nearest phase (12 KB)
-constexpr uint16_t kPrNoRow = 0xffffu;
-
-__host__ __device__ inline uint32_t pr_region_words(uint32_t ndcap, int fill) {
-  const uint32_t a = ndcap + (ndcap + 1) / 2, t = fill ? 3u * kPrTile : 0u;  // vox u32 + row table u16
-  return a > t ? a : t;
-}
-static size_t pr_lds_bytes(uint32_t ndcap, int fill) {
-  // points | vox + row table (nearest: row-mean tile) | nearest: rows, list
-  return sizeof(float) * 3 * kPrPts + 4 * (size_t)pr_region_words(ndcap, fill) +
-         (fill ? (sizeof(int32_t) + sizeof(uint16_t)) * kPrPts : 0);
-}
-
-__global__ void __launch_bounds__(kPrThreads) k_point_rows(const float* __restrict__ pts, const CloudCtl* ctl,
-                                                          const uint32_t* __restrict__ vox_all,
-                                                          const uint8_t* __restrict__ alive_all,
-                                                          const float* __restrict__ rows_block, int32_t* __restrict__ out,
-                                                          uint64_t n, uint32_t ndcap, uint64_t kdes, int fill,
-                                                          const int32_t* __restrict__ counts) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t pr_smem[];
-  __shared__ uint32_t scratch[16];
-  __shared__ uint32_t s_cut[kWorkers];
-  __shared__ uint32_t s_nun;
-  const int b = blockIdx.y;
-  const uint32_t t = threadIdx.x;
-  const CloudCtl& c = ctl[b];
-  const uint64_t start = (uint64_t)blockIdx.x * kPrPts;
-  const uint32_t cnt = (uint32_t)(n - start < (uint64_t)kPrPts ? n - start : (uint64_t)kPrPts);
-  int32_t* o = out + (uint64_t)b * n + start;
-  const uint32_t nout = c.num_out < kdes ? c.num_out : (uint32_t)kdes;  // rows of the level last run
-  if (c.state != kAccepted || c.rc != 0 || nout == 0 || c.num_nds == 0) {  // a cloud without rows
-#pragma unroll
-    for (int q = 0; q < kPrPPT; q++) {
-      const uint32_t il = t + kPrThreads * q;
-      if (il < cnt) o[il] = -1;
-    }
-    return;
-  }
-  float* sp = (float*)pr_smem;                        // [3 * kPrPts]
-  uint32_t* s_vox = pr_smem + 3 * kPrPts;             // [nd]
-  uint16_t* s_row = (uint16_t*)(s_vox + ndcap);       // [nd] row of dense id (< k <= 13653), or kPrNoRow
-  float* s_mean = (float*)s_vox;                      // nearest: [3 * kPrTile]
-  int32_t* s_prow = (int32_t*)(pr_smem + 3 * kPrPts + pr_region_words(ndcap, fill));  // nearest: [kPrPts]
-  uint16_t* s_un = (uint16_t*)(s_prow + kPrPts);      // nearest: [kPrPts] unassigned local ids
-  const uint32_t nd = c.num_nds < ndcap ? c.num_nds : ndcap;
-  {
-    const float* p = pts + ((uint64_t)b * n + start) * 3;
-    float v[3 * kPrPPT];
-#pragma unroll
-    for (int j = 0; j < 3 * kPrPPT; j++) {
-      const uint32_t f = t + kPrThreads * j;
-      v[j] = f < 3 * cnt ? p[f] : 0.0f;
-    }
-    const uint32_t* vox = vox_all + (uint64_t)b * ndcap;
-    const uint8_t* alive = alive_all + (uint64_t)b * ndcap;
-    uint8_t* s_alive = (uint8_t*)s_row;  // [nd], consumed before the row table takes its place
-#pragma unroll 4
-    for (uint32_t d = t; d < nd; d += kPrThreads) {  // (no barrier inside: the loads stay in flight together)
-      s_vox[d] = vox[d];
-      s_alive[d] = alive[d];
-    }
-    if (t < (uint32_t)kWorkers) s_cut[t] = c.first_bad[t];
-    if (t == 0) s_nun = 0;
-#pragma unroll
-    for (int j = 0; j < 3 * kPrPPT; j++) sp[t + kPrThreads * j] = v[j];
-  }
-  __syncthreads();
-  {
-    // row of dense id: thread t owns `per` consecutive NDs (<= 64: ndcap <= 16384), its alive
-    // flags in a register mask, one block scan of the counts
-    const uint32_t per = (nd + kPrThreads - 1) / kPrThreads, d0 = t * per;
-    const uint8_t* s_alive = (const uint8_t*)s_row;
-    unsigned long long live = 0;
-    for (uint32_t j = 0; j < per; j++)
-      if (d0 + j < nd && s_alive[d0 + j]) live |= 1ull << j;
-    uint32_t tot;
-    uint32_t rw = block_excl_scan((uint32_t)__popcll(live), 0u, AddU32(), scratch, tot);  // (barriers: the flags are read)
-    for (uint32_t j = 0; j < per; j++) {
-      if (d0 + j >= nd) break;
-      const uint32_t l = (uint32_t)(live >> j) & 1u;
-      s_row[d0 + j] = l && rw < nout ? (uint16_t)rw : kPrNoRow;
-      rw += l;
-    }
-  }
-  __syncthreads();
-  // the key constants as k_front's search passes derive them
-  const double vs = c.vs, inv_vs = 1.0 / vs;
-  const double off[3] = {c.off[0], c.off[1], c.off[2]};
-  const uint32_t len[3] = {c.len[0], c.len[1], c.len[2]};
-  const float off32[3] = {(float)off[0], (float)off[1], (float)off[2]};
-  const float inv32 = (float)inv_vs;
-  const float lenf[3] = {(float)len[0], (float)len[1], (float)len[2]};
-  const float lmax = fmaxf(lenf[0], fmaxf(lenf[1], lenf[2]));
-  const float half_tol = 0.5f - lmax * 0x1p-19f;
-  const bool fast32 = (double)off32[0] == off[0] && (double)off32[1] == off[1] && (double)off32[2] == off[2];
-  // ragged batches: the cloud's own count for the tail and the workers (a
-  // cloud with rows has a valid count); a point at or past it is padding --
-  // whatever it holds, it gets -1 and never joins the nearest list
-  const uint64_t nc = cloud_points(counts, b, n);
-  const uint64_t chunk = nc / kWorkers, n8 = chunk * kWorkers;
-#pragma unroll
-  for (int q = 0; q < kPrPPT; q++) {
-    const uint32_t il = t + kPrThreads * q;
-    const uint64_t i = start + il;
-    const float x = sp[3 * il], y = sp[3 * il + 1], z = sp[3 * il + 2];
-    const bool finite = i < nc && isfinite(x) && isfinite(y) && isfinite(z);
-    // a point of the run is never below the grid offset (the cloud's minimum); one that is
-    // (a caller's other points) takes the double path, which finds it out of grid
-    const bool below = x < off32[0] || y < off32[1] || z < off32[2];
-    uint32_t key = kKeyRedo;
-    if (fast32 && !below) key = voxel_key_f32(x, y, z, off32, inv32, half_tol, lenf, len);
-    if (__any(key == kKeyRedo)) {  // (voxel_key votes across the wave: every lane enters)
-      const uint32_t k64 = voxel_key((double)x, (double)y, (double)z, off, len, vs, inv_vs);
-      if (key == kKeyRedo) key = k64;
-    }
-    int32_t row = -1;
-    const uint32_t w = i < n8 ? (uint32_t)(i / chunk) : 0u;  // (i < n8: chunk > 0 and w < 8)
-    if (il < cnt && finite && i < n8 && i < s_cut[w] && key != kInvalid) {
-      uint32_t lo = 0, hi = nd;  // first d with vox[d] >= key
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (s_vox[mid] < key) lo = mid + 1;
-        else hi = mid;
-      }
-      if (lo < nd && s_vox[lo] == key && s_row[lo] != kPrNoRow) row = (int32_t)s_row[lo];
-    }
-    if (!fill) {
-      if (il < cnt) o[il] = row;
-    } else {
-      s_prow[il] = row;
-      if (il < cnt && row < 0 && finite) s_un[atomicAdd(&s_nun, 1u)] = (uint16_t)il;
-    }
-  }
-  if (!fill) return;
-  __syncthreads();
-  const uint32_t nun = s_nun;  // (block-uniform; vox and the row table are dead from here)
-  if (nun) {
-    uint32_t L = 1;
-    while (L < 64 && 2 * L * nun <= (uint32_t)kPrThreads) L <<= 1;
-    const uint32_t per = kPrThreads / L, grp = t / L, gl = t & (L - 1);
-    const float* rb = rows_block + (uint64_t)b * kdes * 12;
-    const uint32_t ntile = (nout + kPrTile - 1) / kPrTile;
-    for (uint32_t u0 = 0; u0 < nun; u0 += per) {
-      const uint32_t u = u0 + grp;
-      const uint32_t il = u < nun ? s_un[u] : 0u;
-      const float x = sp[3 * il], y = sp[3 * il + 1], z = sp[3 * il + 2];
-      float bd = __builtin_inff();
-      uint32_t br = 0x7fffffffu;
-      for (uint32_t tl = 0; tl < ntile; tl++) {
-        const uint32_t r0 = tl * kPrTile;
-        const uint32_t nr = nout - r0 < (uint32_t)kPrTile ? nout - r0 : (uint32_t)kPrTile;
-        if (ntile > 1 || u0 == 0) {  // one tile: staged once
-          if (ntile > 1) __syncthreads();
-          for (uint32_t f = t; f < 3 * nr; f += kPrThreads) s_mean[f] = rb[(uint64_t)(r0 + f / 3) * 12 + f % 3];
-          __syncthreads();
-        }
-#pragma unroll 4
-        for (uint32_t r = gl; r < nr; r += L) {  // ascending rows: the strict < keeps the lowest on a tie
-          const float dx = x - s_mean[3 * r], dy = y - s_mean[3 * r + 1], dz = z - s_mean[3 * r + 2];
-          float d = dx * dx;
-          d = d + dy * dy;
-          d = d + dz * dz;
-          if (d < bd) {
-            bd = d;
-            br = r0 + r;
-          }
-        }
-      }
-      for (uint32_t m = 1; m < L; m <<= 1) {  // the group's minimum, the lowest row on a tie
-        const float od = __shfl_xor(bd, (int)m, 64);
-        const uint32_t orow = __shfl_xor(br, (int)m, 64);
-        if (od < bd || (od == bd && orow < br)) {
-          bd = od;
-          br = orow;
-        }
-      }
-      // every distance +inf (coordinates near FLT_MAX): row 0, the lowest of the tie
-      if (gl == 0 && u < nun) s_prow[il] = br == 0x7fffffffu ? 0 : (int32_t)br;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < kPrPPT; q++) {
-    const uint32_t il = t + kPrThreads * q;
-    if (il < cnt) o[il] = s_prow[il];
-  }
-}
+#include "ndt_point_rows.h"
 
 }  // namespace
 
 // ------------------------------------------------------------------ C ABI
-
-extern "C" {
-
-}  // extern "C" (reopened below)
 
 namespace {
 
@@ -5051,52 +4220,34 @@ int ndnet_ndt_plan_create(int batch, uint64_t num_points, uint64_t num_desired, 
     }
     e = hipMemcpy(P->rtab, rt.data(), rt.size() * sizeof(double), hipMemcpyHostToDevice);
   }
+  P->wq_grid = P->cus > 0 ? (uint32_t)P->cus * NDNET_WQ_WPC : 1u;
   {
-    int dv = 0, ncu = 0;
-    if (e == hipSuccess) e = hipGetDevice(&dv);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dv);
-#ifndef NDNET_WQ_WPC
-#define NDNET_WQ_WPC 1
-#endif
-    // NDNET_WQ_WPC workgroups per CU (1, 2 and 3 measured equal on C2 and C5:
-    // profiles/r02c_welford_parts.txt -- the kernel is issue-bound, not
-    // latency-bound, so a second wave per SIMD shares the same issue slots)
-    P->wq_grid = ncu > 0 ? (uint32_t)ncu * NDNET_WQ_WPC : 1u;
-  }
-  {
+    // the dynamic LDS every kernel may be launched with
     const int wq_dyn = (int)(kWqRt * wq_rt_bytes(true) + 8 * ((batch + 1 + 3) & ~3) + kWqHistMax);
-    const void* wqk[] = {(const void*)k_welford_q<float, true>, (const void*)k_welford_q<double, true>,
-                         (const void*)k_welford_q<float, false>, (const void*)k_welford_q<double, false>};
-    for (const void* f : wqk)
-      if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, wq_dyn);
+    const struct {
+      const void* fn;
+      int bytes;
+    } lds[] = {
+        {(const void*)k_welford_q<float, true>, wq_dyn},
+        {(const void*)k_welford_q<double, true>, wq_dyn},
+        {(const void*)k_welford_q<float, false>, wq_dyn},
+        {(const void*)k_welford_q<double, false>, wq_dyn},
+        {(const void*)k_kl_merge<2>, (int)(2 * kMergeLdsChunks * kChunk * sizeof(unsigned long long))},
+        {(const void*)k_kl_merge<1, kMergeRuns1>, (int)(kMergeScoreChunks * kChunk * sizeof(unsigned long long))},
+        {(const void*)k_kl_merge<2, kMergeRuns, true>, (int)kKLFusedLds},
+        {(const void*)k_kl_merge<1, kMergeRuns1, true>, (int)kKLFusedLds},
+        {(const void*)k_kl_merge<0, kMergeRuns, true>, (int)kKLFusedLds},
+        {(const void*)k_kl, kKLLdsMax},
+        {(const void*)k_kl_sort, kKLLdsMax},
+        {(const void*)k_kl_rank_sort<true>, kKLLdsMax},
+        {(const void*)k_kl_rank_sort<false>, kKLLdsMax},
+        {(const void*)k_prune, kKLLdsMax},
+        {(const void*)k_bin_count, (int)(16384 * sizeof(uint32_t))},
+        {(const void*)k_point_rows, (int)pr_lds_bytes(16384, 1)},  // (ndcap <= 16384: 132 KB at most)
+    };
+    for (const auto& a : lds)
+      if (e == hipSuccess) e = hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes);
   }
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_kl_merge<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(2 * kMergeLdsChunks * kChunk * sizeof(unsigned long long)));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_kl_merge<1, kMergeRuns1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(kMergeScoreChunks * kChunk * sizeof(unsigned long long)));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_kl_merge<2, kMergeRuns, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kKLFusedLds);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_kl_merge<1, kMergeRuns1, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kKLFusedLds);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_kl_merge<0, kMergeRuns, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kKLFusedLds);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_kl, hipFuncAttributeMaxDynamicSharedMemorySize, kKLLdsMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_kl_sort, hipFuncAttributeMaxDynamicSharedMemorySize, kKLLdsMax);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_kl_rank_sort<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kKLLdsMax);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute((const void*)k_kl_rank_sort<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kKLLdsMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_prune, hipFuncAttributeMaxDynamicSharedMemorySize, kKLLdsMax);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_bin_count, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)(16384 * sizeof(uint32_t)));
-  if (e == hipSuccess)  // (ndcap <= 16384: 132 KB at most)
-    e = hipFuncSetAttribute((const void*)k_point_rows, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)pr_lds_bytes(16384, 1));
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     fprintf(stderr, "ndnet_amd: plan allocation failed: %s\n", hipGetErrorString(e));

@@ -546,9 +546,6 @@ __device__ __attribute__((always_inline)) inline void mma_kgroup_x6(f32x4 (&acc)
                                                                     int rstride, const bf16x8 (&bw)[NB][kPlanes<T>]) {
   bf16x8 a[RB];
   auto ld = [&](int p) {
-#ifdef NDNET_PN_EXP_NOA  // timing experiment only (wrong results): A fragments from registers
-    if (p != 1) return;
-#endif
 #pragma unroll
     for (int rb = 0; rb < RB; rb++) a[rb] = *reinterpret_cast<const bf16x8*>(a0 + p * plane + rb * rstride);
   };
@@ -623,9 +620,6 @@ __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[
   };
   constexpr int NPL = kPlanes<T>;
   auto load = [&](bf16x8 (&bw)[NB][NPL]) {
-#ifdef NDNET_PN_EXP_NOB  // timing experiment only (wrong results): weights loaded once per layer
-    if (lleft == NT)
-#endif
 #pragma unroll
     for (int j = 0; j < NB; j++)
 #pragma unroll
@@ -922,9 +916,6 @@ __host__ __device__ inline int region_floats(int width, int planes) {
 // layer's bias and (chain B) the TNet(3) tail.  The products are fp32 FMAs
 // (k ascending); the MFMA path computed the same sums in another order.
 __host__ __device__ inline bool valu_layer0(const ndnet_pn_chain& A) {
-#ifdef NDNET_PN_NO_VALU0  // A/B: layer 0 on the MFMA path from an LDS input tile
-  return false;
-#endif
   return A.num_layers > 1 && A.L[0].K == 16 && A.L[0].N == 64 && A.L[0].prec == 0 && !A.L[0].fuse_next &&
          A.in_cols <= 12 && A.x_ld % 4 == 0;
 }
@@ -1237,9 +1228,6 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
     } else {
       __syncthreads();
     }
-#elif defined(NDNET_PN_LBAR)  // A/B: the layer barrier without the vmcnt drain, no prefetch
-    if (l + 1 < A.num_layers) layer_barrier();
-    else __syncthreads();
 #else
     __syncthreads();
 #endif

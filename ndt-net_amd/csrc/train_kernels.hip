@@ -588,7 +588,7 @@ __global__ __launch_bounds__(T) void k_tr_bn_fwd(const float* __restrict__ y, fl
   // clouds in order), merged into pk when the cloud changes.  (A wave-level
   // merge -- the leaving lanes' maxima reduced over the wave, one atomic --
   // measured slower: 39 -> 46 us per 1024-channel launch, r05o; the per-lane
-  // atomics cost ~10 of the 39, NDNET_TR_EXP_NOPOOLATOMIC, r05n.)
+  // atomics cost ~10 of the 39, r05n.)
   unsigned long long best = 0ull;
   int cur = -1;
   auto emit = [&](const ChanWalk<T>& w, float o) {
@@ -597,9 +597,7 @@ __global__ __launch_bounds__(T) void k_tr_bn_fwd(const float* __restrict__ y, fl
       return;
     }
     if (w.b != cur) {
-#ifndef NDNET_TR_EXP_NOPOOLATOMIC  // timing experiment only (wrong pooled values): no LDS atomics
       if (cur >= 0) atomicMax(&pk[cur], best);
-#endif
       cur = w.b;
       best = 0ull;
     }

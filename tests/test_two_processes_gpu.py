@@ -1,7 +1,7 @@
 """Two processes, one GPU, each with its own full-chip NDT plan (VERDICT r5
 item 6).
 
-The front lanes (csrc/ndt_kernels.hip front_launch) order the k_front
+The front lanes (csrc/ndt_front_lanes.h front_launch) order the k_front
 launches of ONE process.  Two processes on one card do not see each other's
 lanes, so their share-1 k_front grids (16 x 16 workgroups: the whole chip
 each) run at once.  k_front deals a launch's clouds cloud-major within each

@@ -223,7 +223,8 @@ static void rung(const char* name) {
   printf("%-44s: %.2f cycles per sample\n", name, (double)c / ((double)(kIters / 8) * 64));
 }
 
-// ---- k_welford_q's heavy-ND loop (copied from csrc/ndt_kernels.hip) alone on one wave ----
+// ---- k_welford_q's heavy-ND loop alone on one wave: the round-4 form with the (rc, rl) table read by scalar
+//      loads, since retired from csrc/ndt_kernels.hip for the LDS row (profiles/r04_wq_rtab.txt) ----
 typedef unsigned int hv_u16 __attribute__((ext_vector_type(16)));
 typedef double hv_d2 __attribute__((ext_vector_type(2)));  // native vector (HIP's double2 is a struct)
 
