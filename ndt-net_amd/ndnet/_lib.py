@@ -123,6 +123,8 @@ EXPORTS = {
     # include/ndnet_augment.h
     "ndnet_aug_work_bytes": (ctypes.c_size_t, [_I, _U64]),
     "ndnet_aug_run": (_I, [_P, _P, _P, _P, _I, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    # include/ndnet_packed.h
+    "ndnet_pts_unpack_i16": (_I, [_P, _P, _I, _U64, _P, _P, _P]),
     "ndnet_ndt_debug_dump": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ndnet_ndt_debug_set_epoch": (_I, [_P, ctypes.c_uint32]),
     "ndnet_ndt_debug_set_kl_fuse": (_I, [_P, _I]),

@@ -1,1 +1,1 @@
-from .carla_seg import CARLA_Seg, collate_padded  # noqa: F401
+from .carla_seg import CARLA_Seg, collate_packed, collate_padded  # noqa: F401

@@ -111,6 +111,19 @@ def collate_padded(batch) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     return points, classes, counts
 
 
+def collate_packed(batch, step=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``collate_padded`` with the points packed for the copy to the GPU
+    (``ndnet.packed.pack_points(points, counts, step)``, run here by the
+    ``DataLoader``'s workers): ``(q [B, n_max, 3] int16, classes [B, n_max]
+    int64, counts [B] int32, qparams [B, 4] float32)`` -- half the bytes of
+    the float32 points.  ``functools.partial(collate_packed, step=...)`` fixes
+    the step; the default takes each scan's own."""
+    from ..packed import pack_points
+    points, classes, counts = collate_padded(batch)
+    q, qparams = pack_points(points, counts, step)
+    return q, classes, counts, qparams
+
+
 def loader(dataset: Dataset, batch_size: int, shuffle: bool = True, num_workers: int = 4, collate_fn=None):
     """DataLoader as train.py:134-137 builds it: worker processes parse ahead
     of the GPU, batches land in pinned memory for non-blocking H2D copies.

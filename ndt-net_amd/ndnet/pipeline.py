@@ -23,7 +23,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib, segment
+from . import _lib, packed as _packed, segment
 from .preprocessing.ndtnet_preprocessing import NdtPlan, check_counts, ndt_multiscale, ndt_preprocessing, get_plan
 
 
@@ -109,6 +109,29 @@ class _Pinned:
         self.sig = self.cache["sig"]
 
 
+def _check_packed_input(is_packed: bool, points, qparams, batch: int, what: str) -> None:
+    """The host's check of what is about to be copied into a graph's or a
+    pipeline's input buffers (``ValueError``, before any GPU work): a packed
+    one takes int16 points together with their float32 ``[batch, 4]``
+    ``qparams``, any other no ``qparams`` at all."""
+    if not is_packed:
+        if qparams is not None:
+            raise ValueError("qparams need packed=True")
+        return
+    if points is None:
+        if qparams is not None:
+            raise ValueError("qparams belong to packed points: give both or neither")
+        return
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.int16:
+        raise ValueError(f"packed=True takes int16 {what} (ndnet.packed.pack_points), got "
+                         f"{getattr(points, 'dtype', type(points))}")
+    if qparams is None:
+        raise ValueError(f"packed {what} need their qparams")
+    if not isinstance(qparams, torch.Tensor) or qparams.dtype != torch.float32 or tuple(qparams.shape) != (batch, 4):
+        raise ValueError(f"qparams must be a float32 tensor of shape ({batch}, 4), got "
+                         f"{getattr(qparams, 'dtype', type(qparams))} {tuple(getattr(qparams, 'shape', ()))}")
+
+
 class GraphedSegmentation:
     """Replays ``model(*ndt_preprocessing(num_nds, points)[:2])`` from a graph.
 
@@ -143,6 +166,16 @@ class GraphedSegmentation:
             scans of any lengths up to ``num_points`` -- with ``levels`` and
             with ``point_labels`` too (padding points get row and label -1).
             The kernels read the counts on the device at replay.
+        packed: ``True`` takes packed scans (``ndnet.packed``): ``self.points``
+            is then the static int16 ``[batch, num_points, 3]`` buffer and
+            ``self.qparams`` the float32 ``[batch, 4]`` one (initialised to
+            origin 0, step 1), and the captured step begins with the decode
+            (``ndnet.packed.unpack``, with the counts when ``ragged``) into a
+            private float32 buffer that everything after it reads.  The
+            outputs are those of the float32 graph on the decoded cloud, bit
+            for bit.  ``__call__(points, counts, qparams=)`` copies all three
+            in (``ValueError`` for points that are not int16 or come without
+            their ``qparams``).  ``False`` (default): the graph as ever.
 
     ``points`` is the static float32 input buffer; ``__call__(new_points)``
     copies into it, replays, and returns the static ``[B, num_nds, C+1]``
@@ -162,9 +195,11 @@ class GraphedSegmentation:
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,
                  device: Optional[torch.device] = None, warmup: int = 2, levels=None,
-                 point_labels: Optional[str] = None, ragged: bool = False) -> None:
+                 point_labels: Optional[str] = None, ragged: bool = False, packed: bool = False) -> None:
         if not isinstance(ragged, bool):  # (checked before any GPU work)
             raise ValueError(f"ragged must be True or False, got {ragged!r}")
+        if not isinstance(packed, bool):
+            raise ValueError(f"packed must be True or False, got {packed!r}")
         if point_labels is not None:
             from .models.ndtnet import NDTNetSegmentation
             if point_labels not in _lib.POINT_FILL:
@@ -183,7 +218,13 @@ class GraphedSegmentation:
         if self.levels:
             num_nds = self.levels[0]
         self.model, self.num_nds, self.device = model, int(num_nds), dev
-        self.points = torch.zeros((batch, num_points, 3), dtype=torch.float32, device=dev)
+        self.packed = packed
+        self.points = torch.zeros((batch, num_points, 3), dtype=torch.int16 if packed else torch.float32, device=dev)
+        # packed: the decode's output, what the rest of the step reads as its points
+        self.qparams = self._decoded = None
+        if packed:
+            self.qparams = torch.tensor([[0.0, 0.0, 0.0, 1.0]] * batch, dtype=torch.float32, device=dev)
+            self._decoded = torch.zeros((batch, num_points, 3), dtype=torch.float32, device=dev)
         self.ragged = ragged
         self.counts = torch.full((batch,), num_points, dtype=torch.int32, device=dev) if ragged else None
         self.fill = point_labels
@@ -206,12 +247,15 @@ class GraphedSegmentation:
         self._pinned = _Pinned(model, [self.plan])
 
     def _step(self):
+        points = self.points
+        if self.packed:
+            points = _packed.unpack(self.points, self.qparams, counts=self.counts, out=self._decoded)
         if self.levels:
-            return [self.model(p, c) for p, c, _ in ndt_multiscale(self.levels, self.points, counts=self.counts)]
-        p, c, _ = ndt_preprocessing(self.num_nds, self.points, counts=self.counts)
+            return [self.model(p, c) for p, c, _ in ndt_multiscale(self.levels, points, counts=self.counts)]
+        p, c, _ = ndt_preprocessing(self.num_nds, points, counts=self.counts)
         out = self.model(p, c)
         if self.fill is not None:
-            rows = segment.point_rows(self.points, self.fill, ndt_preprocessing.last_plan,
+            rows = segment.point_rows(points, self.fill, ndt_preprocessing.last_plan,
                                       ndt_preprocessing.last_rows, out=self.point_rows, counts=self.counts)
             segment.point_labels(out, rows, out=self.point_labels, nd_labels=self._nd_labels)
         return out
@@ -221,11 +265,12 @@ class GraphedSegmentation:
         self.graph.replay()
         return self.out
 
-    def __call__(self, points: Optional[torch.Tensor] = None, counts=None) -> torch.Tensor:
+    def __call__(self, points: Optional[torch.Tensor] = None, counts=None, qparams=None) -> torch.Tensor:
         if counts is not None:
             if not self.ragged:
                 raise ValueError("counts need a graph built with ragged=True")
             check_counts(counts, self.points.shape[0], self.points.shape[1])
+        _check_packed_input(self.packed, points, qparams, self.points.shape[0], "points")
         if points is not None:
             if self.ragged and points.dim() == 3 and points.shape[1] < self.points.shape[1]:
                 self.points[:, :points.shape[1]].copy_(points, non_blocking=True)
@@ -233,6 +278,8 @@ class GraphedSegmentation:
                 self.points.copy_(points, non_blocking=True)
         if counts is not None:
             self.counts.copy_(torch.as_tensor(counts).to(torch.int32), non_blocking=True)
+        if qparams is not None:
+            self.qparams.copy_(qparams, non_blocking=True)
         return self.replay()
 
     def stats(self) -> list:
@@ -325,15 +372,38 @@ class PipelinedSegmentation:
     is written on forward stream j % F only (R is a multiple of F: stream
     order), and a forward waits for the device-to-host copy of the labels it
     overwrites.  Every stage graph stays one linear chain on its own stream.
+
+    ``packed=True``: packed scans in (``ndnet.packed``), half the bytes of the
+    copy that bounds the streamed loop.  ``inputs`` is then a ring of R int16
+    buffers and ``qparam_bufs`` a ring of R float32 ``[batch, 4]`` buffers that
+    travels with them exactly as ``count_bufs`` do (``qparams`` is the one the
+    next step reads; ``load_resident(points, counts, qparams)`` fills all of
+    them; ``replay_streamed(..., qparams_next=)`` copies the next batch's 16
+    bytes per cloud in with its points).  The decode
+    (``ndnet_pts_unpack_i16``, with the counts when ``ragged``) is the first
+    launch of slot j's NDT graph and writes one float32 buffer per NDT stream
+    -- N buffers, not R.  Ring order: decoded buffer j % N is written and read
+    only inside the NDT stages of NDT stream j % N (by the decode, the run, the
+    prune levels and ``k_point_rows``, all in one linear graph), so stream
+    order covers it and no new event is needed; ``inputs[j]`` and
+    ``qparam_bufs[j]`` are read by the decode alone, inside that NDT stage, so
+    ``replay_streamed``'s wait on ``ndt_done`` protects the copy in as it does
+    for float32 inputs.  The outputs are those of the float32 pipeline on the
+    decoded clouds, bit for bit; with ``packed=False`` (default) every graph
+    holds exactly the launches it held before.  ``replay_streamed`` on a
+    packed pipeline raises ``ValueError`` before any GPU work for a
+    ``host_next`` that is not int16 or a missing ``qparams_next``.
     """
 
     def __init__(self, model, num_nds: int, batch: int, num_points: int,
                  device: Optional[torch.device] = None, warmup: int = 2, cu_share: Optional[int] = None,
                  levels=None, fwd_streams: Optional[int] = None, ndt_streams: Optional[int] = None,
                  point_labels: Optional[str] = None, ragged: bool = False,
-                 label_dtype: torch.dtype = torch.int32) -> None:
+                 label_dtype: torch.dtype = torch.int32, packed: bool = False) -> None:
         if not isinstance(ragged, bool):  # (checked before any GPU work, as GraphedSegmentation's)
             raise ValueError(f"ragged must be True or False, got {ragged!r}")
+        if not isinstance(packed, bool):
+            raise ValueError(f"packed must be True or False, got {packed!r}")
         if label_dtype not in (torch.int32, torch.uint8):
             raise ValueError(f"label_dtype must be torch.int32 or torch.uint8, got {label_dtype!r}")
         if point_labels is not None:
@@ -366,7 +436,17 @@ class PipelinedSegmentation:
         self.N = N = max(1, int(ndt_streams if ndt_streams is not None else PIPE_NDT_STREAMS))
         lcm = F * N // math.gcd(F, N)
         self.R = R = -(-(F + N + 1) // lcm) * lcm
-        self.inputs = [torch.zeros((batch, num_points, 3), dtype=torch.float32, device=dev) for _ in range(R)]
+        self.packed = packed
+        self.inputs = [torch.zeros((batch, num_points, 3), dtype=torch.int16 if packed else torch.float32, device=dev)
+                       for _ in range(R)]
+        # packed: the (origin, step) of slot j's batch, read with its int16 input by
+        # the decode at the head of its NDT stage alone; the decoded float32 cloud
+        # lives and dies inside that stage, so one buffer per NDT stream
+        self.qparam_bufs = self._decoded = None
+        if packed:
+            self.qparam_bufs = [torch.tensor([[0.0, 0.0, 0.0, 1.0]] * batch, dtype=torch.float32, device=dev)
+                                for _ in range(R)]
+            self._decoded = [torch.zeros((batch, num_points, 3), dtype=torch.float32, device=dev) for _ in range(N)]
         self.rows = [[torch.zeros((batch, k, 12), dtype=torch.float32, device=dev)
                       for k in (self.levels or (self.num_nds,))] for _ in range(R)]
         # ragged: the counts of slot j's batch, read by its NDT stage alone
@@ -463,13 +543,16 @@ class PipelinedSegmentation:
         """The NDT stage of ring slot j on the current stream, with plan j % N."""
         rows, plan = self.rows[j], self.plans[j % self.N]
         counts = self.count_bufs[j] if self.ragged else None
-        plan.run(self.inputs[j], None, rows[0], None, counts=counts)
+        points = self.inputs[j]
+        if self.packed:
+            points = _packed.unpack(points, self.qparam_bufs[j], counts=counts, out=self._decoded[j % self.N])
+        plan.run(points, None, rows[0], None, counts=counts)
         for k, blk in zip(self.levels[1:] if self.levels else (), rows[1:]):
             plan.prune(k, blk)
         if self.fill is not None:
             # here, while plan j % N still holds this batch's state: the NDT stage
             # of step i + N overwrites it, possibly before this batch's forward ends
-            plan.point_rows(self.inputs[j], rows[0], self.num_nds, self.fill, out=self.point_rows[j], counts=counts)
+            plan.point_rows(points, rows[0], self.num_nds, self.fill, out=self.point_rows[j], counts=counts)
 
     def _fwd(self, j: int):
         """The forward stage of ring slot j: the rows of slot j - 1, in
@@ -526,6 +609,11 @@ class PipelinedSegmentation:
         return self.count_bufs[self.i % self.R] if self.ragged else None
 
     @property
+    def qparams(self) -> Optional[torch.Tensor]:
+        """The ``(ox, oy, oz, step)`` buffer the next step reads (``packed=True``; else None)."""
+        return self.qparam_bufs[self.i % self.R] if self.packed else None
+
+    @property
     def point_labels(self) -> Optional[torch.Tensor]:
         """The label buffer of the step last enqueued (``point_labels=``; else None)."""
         return self.labels[(self.i - 1) % self.R] if self.fill is not None else None
@@ -537,13 +625,18 @@ class PipelinedSegmentation:
         check_counts(counts, self.inputs[0].shape[0], self.inputs[0].shape[1])
         return torch.as_tensor(counts).to(torch.int32)
 
-    def load_resident(self, points: torch.Tensor, counts=None) -> None:
+    def load_resident(self, points: torch.Tensor, counts=None, qparams=None) -> None:
         """Fill every input buffer (every later step re-reads this batch) and,
-        with ``counts``, every count buffer (None leaves them as they are)."""
+        with ``counts``, every count buffer (None leaves them as they are).
+        A packed pipeline takes int16 ``points`` with their ``qparams``."""
+        _check_packed_input(self.packed, points, qparams, self.inputs[0].shape[0], "points")
         if counts is not None:
             counts = self._host_counts(counts)
         for buf in self.inputs:
             buf.copy_(points)
+        if qparams is not None:
+            for buf in self.qparam_bufs:
+                buf.copy_(qparams)
         if counts is not None:
             for buf in self.count_bufs:
                 buf.copy_(counts)
@@ -569,7 +662,8 @@ class PipelinedSegmentation:
         self._join(j)
         return self.out[j]
 
-    def replay_streamed(self, host_next: torch.Tensor, counts_next=None, labels_host: Optional[torch.Tensor] = None):
+    def replay_streamed(self, host_next: torch.Tensor, counts_next=None, labels_host: Optional[torch.Tensor] = None,
+                        qparams_next: Optional[torch.Tensor] = None):
         """``replay()`` with the H2D copy of the batch after it overlapped.
 
         ``counts_next`` (``ragged=True``): that batch's counts, a CPU tensor,
@@ -577,7 +671,11 @@ class PipelinedSegmentation:
         ``labels_host`` (``point_labels=``): a pinned tensor of the labels'
         shape and dtype that receives this step's labels (the batch before
         this step's) on a copy stream of its own, after this step's forward;
-        ``labels_copied`` is that copy's event, for the caller to wait on."""
+        ``labels_copied`` is that copy's event, for the caller to wait on.
+        ``qparams_next`` (``packed=True``, where ``host_next`` is int16): that
+        batch's ``[batch, 4]`` float32 ``qparams``, a CPU tensor copied in with
+        its points; ``ValueError`` when either is missing or of another dtype."""
+        _check_packed_input(self.packed, host_next, qparams_next, self.inputs[0].shape[0], "host_next")
         if counts_next is not None:
             counts_next = self._host_counts(counts_next)
         if labels_host is not None:
@@ -588,13 +686,16 @@ class PipelinedSegmentation:
                 raise ValueError(f"labels_host must be a pinned {ref.dtype} tensor of shape {tuple(ref.shape)}")
         j, nxt = self.i % self.R, (self.i + 1) % self.R
         out = self.replay()
-        # input nxt: last read by the NDT of step i + 1 - R (the run and k_point_rows,
-        # both inside the NDT stage), finished before this step's join
+        # input nxt: last read by the NDT of step i + 1 - R (the run and k_point_rows
+        # or, packed, the decode with qparams nxt: all inside the NDT stage), finished
+        # before this step's join
         self.s_copy.wait_event(self.ndt_done[nxt])
         with torch.cuda.stream(self.s_copy):
             self.inputs[nxt].copy_(host_next, non_blocking=True)
             if counts_next is not None:
                 self.count_bufs[nxt].copy_(counts_next, non_blocking=True)
+            if qparams_next is not None:
+                self.qparam_bufs[nxt].copy_(qparams_next, non_blocking=True)
             self.copied[nxt].record(self.s_copy)
         if labels_host is not None:
             # labels j: written by this step's forward, next by the forward of step
