@@ -2342,11 +2342,18 @@ __device__ uint32_t prune_and_emit(const KLArgs& A, int b, uint64_t k, uint32_t*
     else stop = nkl0 - (failc - 1);
     const bool poisoned = s_poison != kInvalid && s_poison < stop;
     if (poisoned) stop = s_poison;  // the reference would dereference an uninitialised entry here
+    // The kills are the firsts before the failing one.  The last of them may
+    // sit at position `stop` itself: the bound it was checked against was one
+    // kill larger (f < nkl0 - (c-1) admits f = nkl0 - c), and the check that
+    // fails is the one after it.  That position lies in a walked block (the
+    // failing first, or the list's end, is at or past it).
+    const uint32_t lastc = failc == kInvalid ? to_remove : failc - 1;
+    const uint32_t kstop = (!poisoned && failc != kInvalid && stop < nkl0) ? stop + 1 : stop;
     if (threadIdx.x == 0) s_kills = 0;
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < stop; i += blockDim.x) {
+    for (uint32_t i = threadIdx.x; i < kstop; i += blockDim.x) {
       const uint32_t cth = tmp[i];
-      if (cth) {
+      if (cth && cth <= lastc) {
         alive[op[i]] = 0;
         atomicMax(&s_kills, cth);
       }

@@ -73,13 +73,14 @@ class _Run:
     pass
 
 
-def _run(pts, counts, k=K, path=0, labels=None, ncls=-1, tune=None, dumps=True):
-    """One run of a new plan.  counts: a sequence (sent as a device tensor, so no host check) or None."""
+def _run(pts, counts, k=K, path=0, labels=None, ncls=-1, tune=None, dumps=True, vcap=0):
+    """One run of a new plan.  counts: a sequence (sent as a device tensor, so no host check) or None;
+    vcap: the plan's voxel capacity (0: the default)."""
     import torch
     from ndnet.preprocessing.ndtnet_preprocessing import NdtPlan
     B, n, _ = pts.shape
     r = _Run()
-    r.plan = plan = NdtPlan(B, n, k, ncls)
+    r.plan = plan = NdtPlan(B, n, k, ncls, vcap)
     if path:
         plan.set_path(path)
         assert plan.path == path
