@@ -65,6 +65,8 @@ class AugConfig(ctypes.Structure):
 
 assert ctypes.sizeof(AugConfig) == 80
 AUG_TILE = 1024  # NDNET_AUG_TILE (include/ndnet_augment.h)
+NN_TILE_POINTS = 1024  # NDNET_NN_* (include/ndnet_nearest.h)
+NN_CHUNK_SAMPLES = 1024
 
 _lib = None
 
@@ -120,6 +122,9 @@ EXPORTS = {
     # include/ndnet_fps.h
     "ndnet_fps_run": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
     "ndnet_fps_run_f64": (_I, [_P, _I, _U64, _U64, _P, _P, _P, _P, _P]),
+    # include/ndnet_nearest.h
+    "ndnet_nearest_sample_run": (_I, [_P, _I, _U64, _P, _P, _U64, _P, _P, _P, _P]),
+    "ndnet_pn_transform3_run": (_I, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, _I, _U64, _P]),
     # include/ndnet_augment.h
     "ndnet_aug_work_bytes": (ctypes.c_size_t, [_I, _U64]),
     "ndnet_aug_run": (_I, [_P, _P, _P, _P, _I, _U64, _P, _P, _P, _P, _P, _P, _P]),

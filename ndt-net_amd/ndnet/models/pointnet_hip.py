@@ -32,6 +32,14 @@ relu(conv1: F -> 512) and relu(conv2: 512 -> 256) as two
 ``ndnet_pn_fc_mfma_run`` launches, then conv3 (256 -> num_classes) and the
 softmax in one ``ndnet_pn_cls_head_run``, which also re-arms the max-pool
 buffer -> probabilities [B, num_classes, 1].
+
+The PointNet-on-FPS baseline (``ndnet.models.pointnet``; ``_Folded.baseline``)
+runs the same chains on [B, N, 3] points.  The reference clamps the transformed
+points, nan_to_num(t1 p), which is not linear, so t1 is not folded into conv1:
+chain A reads the points, fc3 (GEMV) gives t1, ``ndnet_pn_transform3_run``
+(include/ndnet_nearest.h) writes the transformed points, chain B's layer 0 is
+the shared conv1, and chain C folds t2 through it in its prologue and
+publishes the result for chain D.
 """
 from __future__ import annotations
 
@@ -243,6 +251,9 @@ class _Folded:
                             f3=t.fc3.weight.float(), c3=t.fc3.bias.float())
 
             self.seg = hasattr(m, "conv4")  # NDTNetSegmentation; else NDTNetClassification (no BatchNorm in its head)
+            # the PointNet-on-FPS baseline (models/pointnet.py): points only, conv1 has 3 inputs and
+            # stays a shared layer (t1 is applied to the points, ndnet_pn_transform3_run)
+            self.baseline = bool(getattr(fe, "points_only", False))
             F = m.feature_dim
             self.F = F
             # ---- the feature extractor (chains A-C), the same for either model ----
@@ -266,15 +277,21 @@ class _Folded:
             # conv1 of the t1-transformed input: (W1 M(t1))^T = sum_ac t1[a,c] E_ac^T W1^T,
             # M(t1) = blockdiag(t1, kron(t1, I3)) (p' = t1 p, C' = t1 C)
             dev = self.c1wT.device
-            E = torch.zeros((9, 12, 12), device=dev)
-            for a in range(3):
-                for c in range(3):
-                    E[3 * a + c, a, c] = 1.0
-                    for j in range(3):
-                        E[3 * a + c, 3 + 3 * a + j, 3 + 3 * c + j] = 1.0
-            self.t1_basis = torch.matmul(E.transpose(1, 2), self.c1wT).reshape(9, 12 * 64).contiguous()
+            if self.baseline:
+                self.t1_basis = None
+                self.c1T16 = _wT(self.c1w, 16, 64)        # conv1 W^T, K padded 3 -> 16 with zero rows
+            else:
+                E = torch.zeros((9, 12, 12), device=dev)
+                for a in range(3):
+                    for c in range(3):
+                        E[3 * a + c, a, c] = 1.0
+                        for j in range(3):
+                            E[3 * a + c, 3 + 3 * a + j, 3 + 3 * c + j] = 1.0
+                self.t1_basis = torch.matmul(E.transpose(1, 2), self.c1wT).reshape(9, 12 * 64).contiguous()
             # the per-point layers with fragment-major copies (the HIP chains) ...
             self.chain_w = [w for w, _ in self.A + self.B_tail + [self.C_mid, self.C_tail]]
+            if self.baseline:
+                self.chain_w.append(self.c1T16)
             # ... and the wide pooled layers and conv2 in split-bf16 form
             self.wide = [self.A[2][0], self.B_tail[2][0], self.C_tail[0]]
             # the FC layers of the TNet heads, W^T fragment-major for the MFMA GEMV (ndnet_pn_fc_mfma_run)
@@ -414,7 +431,10 @@ class _Folded:
         else:  # the head's conv1 / conv2 rows are the parameters themselves (no BatchNorm)
             src[id(self.h1w)] = (m.conv1, None, 0, self.F)
             src[id(self.h2w)] = (m.conv2, None, 0, 512)
-        add(4, self.t1_basis, fe.conv1, fe.bn1)
+        if self.baseline:
+            wt(self.c1T16, fe.conv1, fe.bn1)
+        else:
+            add(4, self.t1_basis, fe.conv1, fe.bn1)
         for w in self.chain_w:
             layer, bn, k0, K = src[id(w)]
             add(1, self.frag[id(w)], layer, bn, k0, K, *w.shape)
@@ -482,13 +502,14 @@ def _fc_head(g: torch.Tensor, t: dict, dim: int, h1: torch.Tensor, h2: torch.Ten
     return out.view(-1, dim, dim)
 
 
-def _build_chain(n: int, in_cols: int, layers, relus, mode: int, gmax=None, out_cols=0, fuse=()) -> "_Chain":
+def _build_chain(n: int, in_cols: int, layers, relus, mode: int, gmax=None, out_cols=0, fuse=(),
+                 x_ld: int = 12) -> "_Chain":
     """ctypes argument block of one ``ndnet_pn_chain_run`` (x / out set per call).
     ``layers``: (fragment-major weights, per-cloud stride in floats or 0, bias,
     K, N[, prec]) per layer.  Layers in ``fuse`` are produced in 64-column chunks
     straight into the next layer (include/ndnet_pointnet.h)."""
     ch = _Chain()
-    ch.x_ld = 12
+    ch.x_ld = x_ld
     ch.in_cols = in_cols
     ch.num_points = n
     ch.num_layers = len(layers)
@@ -534,7 +555,7 @@ def _use_t32(B: int, n: int, device) -> bool:
 
 
 def _run_chain(ch: "_Chain", x: torch.Tensor, out=None) -> None:
-    assert x.stride(1) == 12 and x.stride(2) == 1 and x.dtype == torch.float32
+    assert x.stride(1) == ch.x_ld and x.stride(2) == 1 and x.dtype == torch.float32
     ch.x = x.data_ptr()
     ch.out = out.data_ptr() if out is not None else None
     if _use_t32(x.shape[0], x.shape[1], x.device):
@@ -581,21 +602,28 @@ class _Workspace:
         self.h1, self.h2 = torch.empty((B, 512), **f32), torch.empty((B, 256), **f32)
         self.t1, self.t2 = torch.empty((B, 9), **f32), torch.empty((B, 4096), **f32)
         self.cvec = torch.empty((B, 512), **f32)        # per-cloud bias of the seg head
+        kin = 3 if W.baseline else 12                   # conv1's input columns
         # per-cloud folded weights: plain W^T for the torch emulation ...
-        self.w1T = torch.empty((B, 12, 64), **f32)      # (W1 M(t1))^T per cloud
-        self.w1t2 = torch.empty((B, 12, 64), **f32)     # (W1 M(t1))^T t2: layer 0 of chains C / D
+        self.w1T = None if W.baseline else torch.empty((B, 12, 64), **f32)  # (W1 M(t1))^T per cloud
+        self.w1t2 = torch.empty((B, kin, 64), **f32)    # (W1 M(t1))^T t2: layer 0 of chains C / D
         self.b1t2 = torch.empty((B, 64), **f32)         # b1^T t2
         # ... and fragment-major for the HIP chains (K of conv1 padded 12 -> 16);
         # the HIP chains C / D fold t2 in their prologue (fold_t2)
-        self.w1f = torch.empty((B, 16 * 64), **f32)
+        self.w1f = None if W.baseline else torch.empty((B, 16 * 64), **f32)
         self.w1t2f = torch.zeros((B, 16 * 64), **f32)   # chain C publishes (W1 M(t1))^T t2 here for chain D
+        if W.baseline:
+            # the transformed points nan_to_num(t1 p) (ndnet_pn_transform3_run), rows of 4 floats so
+            # that chains B-D read them as layer 0's 16-byte row loads; the fourth is never used
+            self.xt = torch.zeros((B, N, 4), **f32)
+            self.pts = None                             # this forward's points (chain A and the transform read them)
+        first = (W.c1T16, W.c1b) if W.baseline else (self.w1T, W.c1b)
         self.specs = [  # torch emulation: (in_cols, [(W^T, bias)], relus, mode, kwargs)
             (3, W.A, (1, 1, 1), 0, dict(gmax=self.g1)),
-            (12, [(self.w1T, W.c1b)] + W.B_tail, (0, 1, 1, 1), 0, dict(gmax=self.g2)),
-            (12, [(self.w1t2, self.b1t2), W.C_mid, W.C_tail], (0, 0, 0), 0, dict(gmax=self.g3)),
+            (kin, [first] + W.B_tail, (0, 1, 1, 1), 0, dict(gmax=self.g2)),
+            (kin, [(self.w1t2, self.b1t2), W.C_mid, W.C_tail], (0, 0, 0), 0, dict(gmax=self.g3)),
         ]
         if W.seg:  # the 512-wide seg conv1 output feeds conv2 chunk by chunk (never stored whole)
-            self.specs.append((12, [(self.w1t2, self.b1t2), (W.s1aT, self.cvec)] + W.D_tail, (0, 1, 1, 1, 0), 1,
+            self.specs.append((kin, [(self.w1t2, self.b1t2), (W.s1aT, self.cvec)] + W.D_tail, (0, 1, 1, 1, 0), 1,
                                dict(out_cols=W.C1, fuse=(1,))))
         self.N = N
         self.structs = {}
@@ -612,10 +640,12 @@ class _Workspace:
                 return (W.frag6[id(w)], 0, b, w.shape[0], w.shape[1], MODES[mode])
             return (W.frag[id(w)], 0, b, w.shape[0], w.shape[1])
 
-        L1 = (self.w1f, self.w1f.stride(0), W.c1b, 16, 64)
+        # conv1: per cloud with t1 folded in; the baseline's is the shared layer (t1 went into the points)
+        L1 = shared((W.c1T16, W.c1b)) if W.baseline else (self.w1f, self.w1f.stride(0), W.c1b, 16, 64)
         # chain C's layer 0: conv1 with t1 and t2 folded (ndnet_pn_fold_t2_run), or
-        # with t1 only and t2 folded in its prologue (NDNET_PN_FOLD_T2=chain)
-        LC = (self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64) if FOLD_T2_KERNEL else L1
+        # with t1 only and t2 folded in its prologue (NDNET_PN_FOLD_T2=chain; always for the
+        # baseline, whose conv1 has no per-cloud copy for ndnet_pn_fold_t2_run to read)
+        LC = (self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64) if FOLD_T2_KERNEL and not W.baseline else L1
         layers = [
             [shared(x) for x in W.A],
             [L1] + [shared(x) for x in W.B_tail],
@@ -637,18 +667,20 @@ class _Workspace:
         structs = self.structs.get(self.mode)
         W = self.W
         if structs is None:
-            structs = self.structs[self.mode] = [_build_chain(self.N, s[0], hl, s[2], s[3], **s[4])
-                                                 for s, hl in zip(self.specs, self.hip_layers(self.mode))]
+            # input rows: [B,N,12] blocks; the baseline's chain A reads the points themselves, B-D ws.xt
+            x_lds = (3, 4, 4, 4) if W.baseline else (12, 12, 12, 12)
+            structs = self.structs[self.mode] = [_build_chain(self.N, s[0], hl, s[2], s[3], x_ld=xl, **s[4])
+                                                 for s, hl, xl in zip(self.specs, self.hip_layers(self.mode), x_lds)]
             if W.seg:  # the last chain re-arms the max-pool buffer (-inf) for the next forward
                 structs[3].clear = self.gbuf.data_ptr()
                 structs[3].clear_count = self.gbuf.numel()
-            if HEAD3_IN_CHAIN:  # chain B computes t1 and its conv1 weights itself
+            if HEAD3_IN_CHAIN and not W.baseline:  # chain B computes t1 and its conv1 weights itself
                 cb = structs[1]
                 cb.head_h2, cb.head_ld, cb.head_K = self.h2.data_ptr(), self.h2.stride(0), self.h2.shape[1]
                 cb.head_w3, cb.head_b3 = W.t1["f3"].data_ptr(), W.t1["c3"].data_ptr()
                 cb.head_basis, cb.head_kin, cb.head_nout = W.t1_basis.data_ptr(), 12, 64
                 cb.head_t1 = self.t1.data_ptr()
-            if not FOLD_T2_KERNEL:  # chain C: t2 through layer 0 (prologue fold), published for chain D
+            if not FOLD_T2_KERNEL or W.baseline:  # chain C: t2 through layer 0 (prologue fold), published for chain D
                 cc = structs[2]
                 cc.fold_t2, cc.fold_ld = self.t2.data_ptr(), self.t2.stride(0)
                 cc.fold_out_w, cc.fold_out_b = self.w1t2f.data_ptr(), self.b1t2.data_ptr()
@@ -745,12 +777,23 @@ def _glue_hip(W, ws, B: int):
                                                ws.w1f[c0].data_ptr(), n, 256, 12, 64, st())
             _lib.check(rc, "ndnet_pn_head3_run")
 
+    def head_a_points():
+        # the baseline: t1 itself (fc3 on the GEMV kernel: 9 outputs, row-major weights), then
+        # nan_to_num(t1 p) for every point -- not linear, so a launch of its own (no fold into conv1)
+        t = W.t1
+        fc(ws.g1, t["f1"], t["c1"], ws.h1, True)
+        fc(ws.h1, t["f2"], t["c2"], ws.h2, True)
+        _fc(ws.h2, t["f3"], t["c3"], ws.t1, False, None)
+        rc = _lib.lib().ndnet_pn_transform3_run(ws.pts.data_ptr(), ws.pts.stride(1), ws.t1.data_ptr(),
+                                                ws.xt.data_ptr(), ws.xt.stride(1), B, ws.pts.shape[1], st())
+        _lib.check(rc, "ndnet_pn_transform3_run")
+
     def head_b():
         t = W.t2
         fc(ws.g2, t["f1"], t["c1"], ws.h1, True)
         fc(ws.h1, t["f2"], t["c2"], ws.h2, True)
         fc(ws.h2, t["f3"], t["c3"], ws.t2, False)  # t2
-        if FOLD_T2_KERNEL:  # t2 through conv1: chains C / D's layer 0, once per cloud
+        if FOLD_T2_KERNEL and not W.baseline:  # t2 through conv1: chains C / D's layer 0, once per cloud
             rc = _lib.lib().ndnet_pn_fold_t2_run(ws.w1f.data_ptr(), ws.w1f.stride(0), W.c1b.data_ptr(),
                                                  ws.t2.data_ptr(), ws.t2.stride(0), ws.w1t2f.data_ptr(),
                                                  ws.b1t2.data_ptr(), B, st())
@@ -768,7 +811,7 @@ def _glue_hip(W, ws, B: int):
                                               ws.gbuf.data_ptr(), ws.gbuf.numel(), st())
         _lib.check(rc, "ndnet_pn_cls_head_run")
 
-    return head_a, head_b, (seg_bias if W.seg else cls_head)
+    return (head_a_points if W.baseline else head_a), head_b, (seg_bias if W.seg else cls_head)
 
 
 def _glue_torch(W, ws, B: int):
@@ -777,9 +820,13 @@ def _glue_torch(W, ws, B: int):
         t1 = _fc_head(ws.g1, W.t1, 3, ws.h1, ws.h2, ws.t1)
         torch.matmul(t1.reshape(B, 9), W.t1_basis, out=ws.w1T.view(B, 12 * 64))
 
+    def head_a_points():
+        t1 = _fc_head(ws.g1, W.t1, 3, ws.h1, ws.h2, ws.t1)
+        ws.xt[..., :3] = torch.nan_to_num(torch.bmm(ws.pts, t1.transpose(1, 2)), nan=0.0)
+
     def head_b():
         t2 = _fc_head(ws.g2, W.t2, 64, ws.h1, ws.h2, ws.t2)
-        torch.matmul(ws.w1T, t2, out=ws.w1t2)
+        torch.matmul(W.c1wT if W.baseline else ws.w1T, t2, out=ws.w1t2)
         torch.matmul(W.c1b[None, None, :], t2, out=ws.b1t2.view(B, 1, 64))
 
     def seg_bias():
@@ -790,7 +837,7 @@ def _glue_torch(W, ws, B: int):
         torch.addmm(W.h2b, ws.h1, W.h2w[:, :, 0].t(), out=ws.h2).relu_()
         out.copy_(torch.softmax(torch.addmm(W.h3b[: W.C], ws.h2, W.h3w[:, :, 0].t()), dim=1))
 
-    return head_a, head_b, (seg_bias if W.seg else cls_head)
+    return (head_a_points if W.baseline else head_a), head_b, (seg_bias if W.seg else cls_head)
 
 
 # Workspace slot of the forwards launched from now on (``workspace_slot``).
@@ -839,16 +886,20 @@ def _features(model, points: torch.Tensor, covariances: torch.Tensor, chain):
     if ws is None:
         ws = cache["ws"][key] = _Workspace(W, B, N, dev, mode)
     ws.mode = mode  # the model's mode as of this forward: its argument blocks are kept per mode
+    if W.baseline:
+        # chain A and the transform read the points ([B,N,3] rows of 3), chains B-D the transformed ones
+        xa = ws.pts = points.float().contiguous()
+        x = ws.xt
     # one [B,N,12] block; ndt_preprocessing already returns views of one
-    if (points.stride() == (N * 12, 12, 1) and covariances.stride() == (N * 12, 12, 1)
+    elif (points.stride() == (N * 12, 12, 1) and covariances.stride() == (N * 12, 12, 1)
             and covariances.data_ptr() == points.data_ptr() + 12 and points.dtype == torch.float32):
-        x = points.as_strided((B, N, 12), (N * 12, 12, 1))
+        xa = x = points.as_strided((B, N, 12), (N * 12, 12, 1))
     else:
-        x = torch.cat((points, covariances), dim=2).float().contiguous()
+        xa = x = torch.cat((points, covariances), dim=2).float().contiguous()
     head_a, head_b, last = (_glue_hip if chain is None else _glue_torch)(W, ws, B)
     if chain is not None:
         ws.gbuf.fill_(float("-inf"))
-    ws.chain(0, x, chain)   # A: TNet(3) -> g1
+    ws.chain(0, xa, chain)  # A: TNet(3) -> g1
     head_a()                # t1, (W1 M(t1))^T
     ws.chain(1, x, chain)   # B: conv1 (+t1) then TNet(64) -> g2
     head_b()                # t2, t2 @ [W2^T | Ws1a^T]

@@ -12,6 +12,12 @@ plain torch.
     conf = confusion(labels, gt, model.num_classes)               # [C + 1, C + 1]
     per_class, mean = iou(conf)
 
+The PointNet-on-FPS baseline (``ndnet.models.pointnet``) is scored the same
+way: ``segment_points_fps`` labels ``n_samples`` farthest-point samples per
+cloud and gives every point the class of its nearest sample.
+
+    labels, log_probs = segment_points_fps(baseline, 4096, points, counts=counts)
+
 ``row_histogram`` goes the other way for training: the points' rows and labels
 give every ND row its class histogram, the target of the point-level loss
 (``ndnet.training.point_loss``).
@@ -23,7 +29,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .preprocessing.fps import _per_cloud
+from .preprocessing.fps import _per_cloud, farthest_point_sample
+from .preprocessing.nearest import nearest_sample
 from .preprocessing.ndtnet_preprocessing import NdtPlan, check_counts, ndt_preprocessing
 
 
@@ -129,6 +136,78 @@ def segment_points(model, num_nds: int, points: torch.Tensor, fill: str = "neare
         log_probs = model(p.to(plan.device), c.to(plan.device))
         rows = point_rows(points, fill, plan, block, counts=ndt_preprocessing.last_counts)
         return point_labels(log_probs, rows), log_probs
+
+
+class FpsSegmentBuffers:
+    """Every intermediate of ``segment_points_fps`` for one batch shape,
+    allocated once: with these the whole sequence allocates nothing but the
+    model's output and can be captured in one ``torch.cuda.graph`` on one
+    stream.  ``indices`` ``[B, S]`` int32 (the FPS picks, -1 past a short
+    cloud's count), ``samples`` ``[B, S, 3]``, ``rows`` ``[B, n]`` int32 (the
+    nearest sample of every point), ``labels`` ``[B, n]`` int32."""
+
+    def __init__(self, B: int, n: int, n_samples: int, device) -> None:
+        S = int(n_samples)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.shape = (int(B), int(n), S)
+        self.indices = torch.empty((B, S), **i32)
+        self.min_dist = torch.empty((B, n), dtype=torch.float32, device=device)
+        self.gather_index = torch.empty((B, S, 3), dtype=torch.int64, device=device)
+        self.samples = torch.empty((B, S, 3), dtype=torch.float32, device=device)
+        self.sample_counts = torch.empty((B,), **i32)
+        self.rows = torch.empty((B, n), **i32)
+        self.nd_labels = torch.empty((B, S), **i32)
+        self.labels = torch.empty((B, n), **i32)
+
+
+def segment_points_fps(model, n_samples: int, points: torch.Tensor, counts=None, start=None,
+                       buffers: Optional[FpsSegmentBuffers] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A class for every point of ``points`` ``[B, n, 3]`` (float32, on the
+    GPU) from the PointNet baseline: ``farthest_point_sample`` picks
+    ``n_samples`` points per cloud, ``model`` (an eval-mode
+    ``PointNetSegmentation``) scores them, ``nearest_sample`` gives every point
+    its nearest sample and ``point_labels`` that sample's class, under
+    ``torch.no_grad()``.
+
+    Returns ``(labels [B, n] int32, log_probs [B, n_samples, C + 1])``.
+
+    ``counts`` (a ``[B]`` tensor or sequence): a ragged batch padded to
+    ``[B, n_max, 3]``; the padding points get -1 (``confusion`` leaves them
+    out).  A cloud with fewer than ``n_samples`` points repeats its first point
+    in the model's input; those copies stand for no point.  ``start``: the
+    first sample of every cloud (``farthest_point_sample``).
+
+    ``buffers`` (``FpsSegmentBuffers`` of this shape): every step writes into
+    it -- the FPS indices, the gather (``torch.gather`` into ``samples``), the
+    rows and the labels, which are then ``buffers.labels`` -- so the sequence
+    is one straight line of launches on the current stream with no allocation
+    but the model's output, and capturable; give ``counts`` / ``start`` as
+    int32 tensors on the device then."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError(f"points must be a [B, n, 3] tensor, got {tuple(getattr(points, 'shape', ()))}")
+    if points.dtype != torch.float32:
+        raise ValueError(f"points must be float32, got {points.dtype}")
+    B, n, _ = points.shape
+    S = int(n_samples)
+    if buffers is not None and buffers.shape != (B, n, S):
+        raise ValueError(f"buffers are for (B, n, n_samples) = {buffers.shape}, got {(B, n, S)}")
+    with torch.no_grad():
+        pts = points.contiguous()
+        buf = buffers if buffers is not None else FpsSegmentBuffers(B, n, S, pts.device)
+        dev = pts.device
+        counts = _per_cloud(counts, B, dev, "counts")
+        farthest_point_sample(pts, S, counts=counts, start=start, out=buf.indices, min_dist=buf.min_dist)
+        # the gather by the picked indices (-1 past a short cloud's count reads point 0)
+        buf.gather_index.copy_(buf.indices.unsqueeze(2).expand(B, S, 3))
+        buf.gather_index.clamp_(min=0)
+        torch.gather(pts, 1, buf.gather_index, out=buf.samples)
+        log_probs = model(buf.samples)
+        sample_counts = None
+        if counts is not None:
+            sample_counts = torch.clamp(counts, max=S, out=buf.sample_counts)
+        nearest_sample(pts, buf.samples, counts=counts, sample_counts=sample_counts, out=buf.rows)
+        labels = point_labels(log_probs, buf.rows, out=buf.labels, nd_labels=buf.nd_labels)
+        return labels, log_probs
 
 
 def confusion(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch.Tensor:
