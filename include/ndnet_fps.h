@@ -44,6 +44,10 @@ extern "C" {
  * d_min_dist and make a round trip through L2 on every sample. */
 #define NDNET_FPS_REG_POINTS_F32 100352
 #define NDNET_FPS_REG_POINTS_F64 49152
+/* The register tier is walked in chunks of this many slabs whose loads are in flight together. */
+#define NDNET_FPS_CHUNK_SLABS_F32 7
+/* The same for double (24 registers of coordinates, against float's 21). */
+#define NDNET_FPS_CHUNK_SLABS_F64 4
 
 /* d_points [B][n][3]; d_counts NULL or [B] int32 with 1 <= d_counts[b] <= n (only the first
  * d_counts[b] points of cloud b exist, the others are never read; a value outside the range

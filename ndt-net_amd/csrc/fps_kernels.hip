@@ -46,11 +46,11 @@ constexpr int kWaves = kT / 64;
 template <typename T> struct FpsCfg;
 template <> struct FpsCfg<float> {
   static constexpr int kRegSlabs = NDNET_FPS_REG_POINTS_F32 / kT, kLdsSlabs = NDNET_FPS_LDS_POINTS_F32 / kT;
-  static constexpr int kChunk = 7;  // slabs whose coordinate loads are in flight together (21 registers)
+  static constexpr int kChunk = NDNET_FPS_CHUNK_SLABS_F32;  // slabs whose coordinate loads are in flight together (21 registers)
 };
 template <> struct FpsCfg<double> {
   static constexpr int kRegSlabs = NDNET_FPS_REG_POINTS_F64 / kT, kLdsSlabs = NDNET_FPS_LDS_POINTS_F64 / kT;
-  static constexpr int kChunk = 4;  // (24 registers)
+  static constexpr int kChunk = NDNET_FPS_CHUNK_SLABS_F64;  // (24 registers)
 };
 static_assert(NDNET_FPS_REG_POINTS_F32 % (kT * FpsCfg<float>::kChunk) == 0, "");
 static_assert(NDNET_FPS_REG_POINTS_F64 % (kT * FpsCfg<double>::kChunk) == 0, "");

@@ -1,5 +1,6 @@
 """numpy oracle of farthest point sampling as include/ndnet_fps.h defines it
-(a helper of test_fps_cpu.py and test_fps_gpu.py, not a conftest).
+(a helper of test_fps_cpu.py, test_fps_gpu.py and the test_fps_cases files,
+not a conftest).
 
 Per cloud, in the points' own dtype, every operation rounded (numpy does not
 fuse separate ufunc calls):

@@ -310,6 +310,52 @@ def test_segment_points_fps_end_to_end_and_captured():
 
 
 @pytest.mark.gpu
+def test_segment_points_fps_with_clouds_shorter_than_n_samples():
+    """Counts 600, 100 and 1 at n_samples = 256: a short cloud's indices end in -1, the model's
+    input repeats its point 0 there, and those copies stand for no point -- every row lies
+    below min(count, n_samples).  The full cloud beside them is scored as when it is alone."""
+    from ndnet import segment
+    B, n, S, counts = 3, 600, 256, [600, 100, 1]
+    m = _model(64, 5)
+    g = torch.Generator().manual_seed(3)
+    pts = torch.rand((B, n, 3), generator=g) * torch.tensor([80.0, 80.0, 6.0]) - torch.tensor([40.0, 40.0, 2.0])
+    for b, c in enumerate(counts):
+        pts[b, c:] = float("nan")
+    pts = pts.cuda()
+    d_counts = torch.tensor(counts, dtype=torch.int32, device="cuda")
+    labels, log_probs = segment.segment_points_fps(m, S, pts, counts=d_counts)
+    buf = segment.FpsSegmentBuffers(B, n, S, pts.device)
+    labels_b, log_probs_b = segment.segment_points_fps(m, S, pts, counts=d_counts, buffers=buf)
+    assert labels_b is buf.labels and torch.equal(labels_b, labels) and torch.equal(log_probs_b, log_probs)
+    assert labels.dtype == torch.int32 and labels.shape == (B, n) and log_probs.shape == (B, S, 6)
+
+    p_np = pts.cpu().numpy()
+    idx, rows, samples = buf.indices.cpu().numpy(), buf.rows.cpu().numpy(), buf.samples.cpu().numpy()
+    assert buf.sample_counts.tolist() == [256, 100, 1]
+    for b, c in enumerate(counts):
+        ms = min(c, S)
+        assert np.array_equal(idx[b], fps_ref(p_np[b], S, c)[0]), b
+        assert (idx[b, :ms] >= 0).all() and (idx[b, ms:] == -1).all()
+        assert np.array_equal(samples[b], p_np[b][np.maximum(idx[b], 0)]), b
+        assert np.array_equal(samples[b, ms:], np.broadcast_to(p_np[b, 0], (S - ms, 3)))  # its first point, repeated
+        assert np.array_equal(rows[b], nearest_ref(p_np[b], samples[b], c, ms)[0]), b
+        assert (rows[b, :c] >= 0).all() and (rows[b, :c] < ms).all() and (rows[b, c:] == -1).all()
+    cls = log_probs.argmax(-1).cpu().numpy()
+    want = np.where(rows >= 0, np.take_along_axis(cls, np.maximum(rows, 0), axis=1), -1)
+    got = labels.cpu().numpy()
+    assert np.array_equal(got, want)
+    for b, c in enumerate(counts):
+        assert (got[b, :c] >= 0).all() and (got[b, c:] == -1).all()
+    with torch.no_grad():
+        assert (log_probs - m.forward_torch(buf.samples)).abs().max().item() < TOL
+    # a short neighbour does not leak into the full cloud
+    l0, lp0 = segment.segment_points_fps(m, S, pts[:1], counts=[600])
+    e = (log_probs[0] - lp0[0]).abs().max().item()
+    print(f"cloud 0 beside short clouds vs alone: log-probs differ by {e:.3e}")
+    assert e < TOL and bool(torch.isfinite(log_probs).all())
+
+
+@pytest.mark.gpu
 def test_ndt_model_is_untouched_by_a_baseline_forward():
     """Workspaces are cached per model: an NDTNetSegmentation forward before and
     after a baseline forward of the same (B, N) gives identical bits."""
