@@ -36,7 +36,11 @@ from .. import _lib
 
 
 def read_ply(path: str, num_classes: int, num_header_lines: int = 10, threads: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-    """(xyz [n, 3] float64, class tags [n] uint16) of an ASCII PLY scan."""
+    """(xyz [n, 3] float64, class tags [n] uint16) of an ASCII PLY scan.  ``ValueError`` for a
+    malformed line or a class tag out of bounds, with the line's 0-based index among the data
+    lines (include/ndnet_ingest.h has the rule)."""
+    if int(num_classes) > 65535:  # the tags are uint16
+        raise ValueError(f"num_classes {num_classes} does not fit the uint16 class tags")
     lib = _lib.lib()
     bpath = os.fsencode(path)
     n = ctypes.c_uint64(0)
