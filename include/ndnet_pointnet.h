@@ -233,6 +233,42 @@ int ndnet_pn_head3_run(const float *h2, int ld_h, const float *W3, const float *
 int ndnet_pn_fold_t2_run(const float *w1f, int w1_stride, const float *b1, const float *t2, int t2_ld, float *outf,
                          float *outb, int batch, void *stream);
 
+/* Chain C (conv1 with t1 and t2 folded, conv2, conv3, max over points) as one
+ * per-cloud 12 -> F layer: no ReLU separates the three (ndtnet.py:149-161),
+ * so with y0 = x W0[b] + b0[b], y1 = y0 w_mid + b_mid, y2 = y1 w_tail + b_tail
+ *   gmax[b][f] = max_n (sum_k x[b][n][k] Wc[b][k][f]) + bc[b][f],   f < Fp,
+ *   Wc[b] = W0[b] w_mid w_tail,  bc[b] = (b0[b] w_mid + b_mid) w_tail + b_tail.
+ * Fp is 32 or a multiple of 64, as a chain layer's N.  One launch of
+ * (ceil(Fp / 64), batch) workgroups.  Each forms its 64 columns of
+ * [Wc; bc] from the tensors as they are at the launch (products in double,
+ * rounded once to fp32; nothing is cached, so an in-place re-fold is picked
+ * up), then streams the cloud's rows: 12 fp32 multiply-adds per point and
+ * column with k ascending (v_mfma_f32_16x16x4_f32, fp32 products and sums),
+ * the maximum over the points, the bias added to the maximum, one plain
+ * store per column.  No atomics: gmax needs no -inf before the
+ * launch and is written only in columns 0 .. Fp - 1 of its rows.
+ *   x       [batch][num_points][x_ld], columns 0..11 read; x_ld >= 12, x_ld % 4 == 0
+ *   w0f     [batch][w0_stride >= 1024]: W0[b] (12 x 64) in the fragment-major K = 16
+ *           layout ndnet_pn_fold_t2_run writes (rows 12..15 are not read)
+ *   b0      [batch][b0_stride >= 64]
+ *   w_mid   W2'^T [64][128] row-major, b_mid [128]
+ *   w_tail  W3'^T [128][Fp] row-major, b_tail [Fp]; columns F .. Fp - 1 of both are zero
+ *           padding, which leaves those columns of gmax at exactly 0
+ *   gmax    [batch][gmax_ld >= Fp]
+ * As the chain's pooled epilogue: a NaN never wins the maximum, -0 is stored
+ * as +0, and a column no row reached is stored as -inf.  A row holding a NaN
+ * or an infinity takes no part (the layered chain's split-bf16 layers turn an
+ * infinite activation into NaNs, which the maximum drops).  Bit-identical
+ * from run to run.  NDNET_ERR_ARG (-20) before any launch for a NULL pointer,
+ * batch outside 1..65535, num_points < 1, a stride below its minimum,
+ * x_ld % 4, F outside 1..Fp, Fp neither 32 nor a multiple of 64, or
+ * gmax_ld < Fp; -21 on a launch
+ * failure.  No allocation, no synchronisation: graph-capturable. */
+int ndnet_pn_pool12_run(const float *x, int x_ld, int num_points, const float *w0f, int64_t w0_stride,
+                        const float *b0, int64_t b0_stride, const float *w_mid, const float *b_mid,
+                        const float *w_tail, const float *b_tail, int F, int Fp, float *gmax, int gmax_ld,
+                        int batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

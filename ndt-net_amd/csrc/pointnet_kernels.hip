@@ -1563,6 +1563,192 @@ __global__ void __launch_bounds__(1024) k_pn_fold_t2(const float* __restrict__ w
   }
 }
 
+#if NDNET_PN_TILE == 64
+// ---- chain C as one per-cloud 12 -> F layer (ndnet_pn_pool12_run) ----
+// NDTNet's conv1 (with t1, t2 folded), conv2 and conv3 have no ReLU between
+// them (ndtnet.py:149-161), so the pooled feature is
+//   g3[b][f] = max_n (sum_k x[b][n][k] Wc[b][k][f]) + bc[b][f],
+//   [Wc[b]; bc[b]] = [W0''[b]; b0''[b]] W2'^T W3'^T  (+ b2' W3'^T + b3' on the bias row)
+// -- 12 multiply-adds per point and column where the layered chain does 64
+// into 128 and 128 into F.  One workgroup per 64 columns of one cloud:
+//   phase 1  its 13 x 64 slice of [Wc; bc], the bias carried as row 12 (as
+//            k_pn_fold_t2 does), on the f64 MFMA from the live folded tensors
+//            (they are re-folded in place after a weight update: no product
+//            of them is kept anywhere), rounded once to fp32;
+//   phase 2  the cloud's rows in 16-point tiles dealt to the 16 waves, a tile
+//            times the slice as three v_mfma_f32_16x16x4_f32 per 16 columns
+//            (fp32 FMAs, k ascending), a running fmaxf per lane from -inf,
+//            one reduction over the lane rows (DPP) and the waves (LDS), the
+//            bias added to the maximum (fl(a + b) is monotonic in a, as
+//            pool_cols relies on), one plain store per column.
+// A row with a NaN or an infinity takes no part in the maximum: chain C's
+// split-bf16 layers turn an infinite layer-0 output into NaN planes, and
+// fmaxf drops the NaNs.  The rows past the cloud's last point enter as NaN
+// rows, dropped the same way.
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+constexpr int kP12Waves = 16;
+constexpr int kP12Pre = 4;     // tiles per wave whose rows are loaded ahead of phase 1 (all of them up to 1024 points)
+constexpr int kP12Pitch = 130; // doubles per row of the 13 x 128 intermediate: phase 1's column reads spread over the banks
+
+// this lane's part of tile `tile`: point 16 tile + cl, columns 4 s + kq.  Loads only (no branch, nothing
+// that waits for them): a lane past the cloud's last point reads the last row, which p12_clean drops
+__device__ inline void p12_rows(const float* __restrict__ xb, int x_ld, int n, int tile, int kq, int cl, float (&v)[3]) {
+  const int p = min(16 * tile + cl, n - 1);
+  const float* r = xb + (int64_t)p * x_ld + kq;
+#pragma unroll
+  for (int s = 0; s < 3; s++) v[s] = r[4 * s];
+}
+
+// ... and what enters the products: NaN for a lane past the cloud and for a NaN or an infinity
+__device__ inline void p12_clean(int n, int tile, int cl, float (&v)[3]) {
+  const bool in = 16 * tile + cl < n;
+#pragma unroll
+  for (int s = 0; s < 3; s++) v[s] = (in & (fabsf(v[s]) < INFINITY)) ? v[s] : NAN;  // & : one select, no branch
+}
+
+__global__ void __launch_bounds__(kP12Waves * 64) k_pn_pool12(
+    const float* __restrict__ x, int x_ld, int n, const float* __restrict__ w0f, int64_t w0_stride,
+    const float* __restrict__ b0, int64_t b0_stride, const float* __restrict__ w_mid,
+    const float* __restrict__ b_mid, const float* __restrict__ w_tail, const float* __restrict__ b_tail, int Fp,
+    float* __restrict__ gmax, int gmax_ld) {
+  __shared__ double s_m[13 * kP12Pitch];     // [W0''; b0''] W2'^T (+ b2' on row 12)
+  __shared__ float s_wc[13 * 64];            // this workgroup's columns of [Wc; bc]
+  __shared__ float s_red[kP12Waves * 64];
+  const int b = blockIdx.y, c0 = 64 * blockIdx.x;
+  const int lane = threadIdx.x & 63, kq = lane >> 4, cl = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int tiles = (n + 15) >> 4;
+  const float* xb = x + (int64_t)b * n * x_ld;
+
+  // the first tiles' rows and phase 1's operands: every load of the kernel's first half in flight at once
+  float xp[kP12Pre][3];
+#pragma unroll
+  for (int i = 0; i < kP12Pre; i++) p12_rows(xb, x_ld, n, wave + kP12Waves * i, kq, cl, xp[i]);
+  float tw[32];  // waves 8..11 (phase 1b): W3'^T[4 ks + kq][c0 + 16 (wave - 8) + cl]
+
+  // phase 1a, waves 0..7, 16 columns of the intermediate each: A = [W0''; b0''] (row cl of 16, 13 used),
+  // B = W2'^T; v_mfma_f64_16x16x4_f64 leaves row kq + 4 q, column cl in element q
+  if (wave < 8) {
+    const float* wb = w0f + (int64_t)b * w0_stride;
+    const float* bb = b0 + (int64_t)b * b0_stride;
+    float a[16], bw[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ks++) {
+      const int i = 4 * ks + kq;  // conv1's output channel: W0'' is fragment-major with K = 16 (k_pn_fold_t2)
+      const float* src = cl < 12 ? wb + ((((i >> 4) * 64 + ((cl >> 2) & 3) * 16 + (i & 15)) << 2) + (cl & 3)) : bb + i;
+      a[ks] = *src;  // rows 13..15 read the bias too and are zeroed below: one load, no branch
+      bw[ks] = w_mid[i * 128 + 16 * wave + cl];
+    }
+#pragma unroll
+    for (int ks = 0; ks < 16; ks++) a[ks] = cl < 13 ? a[ks] : 0.0f;
+    f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < 16; ks += 2) {
+      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[ks], (double)bw[ks], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[ks + 1], (double)bw[ks + 1], acc1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int row = kq + 4 * q, col = 16 * wave + cl;
+      double v = acc0[q] + acc1[q];
+      if (row == 12) v += (double)b_mid[col];
+      if (row < 13) s_m[row * kP12Pitch + col] = v;
+    }
+  } else if (wave < 12) {
+    const int tc = min(c0 + 16 * (wave - 8) + cl, Fp - 1);  // Fp = 32: the upper half's columns are never stored
+#pragma unroll
+    for (int ks = 0; ks < 32; ks++) tw[ks] = w_tail[(int64_t)(4 * ks + kq) * Fp + tc];
+  }
+  __syncthreads();
+  // phase 1b, waves 8..11 (idle in 1a, so their operands are already here), 16 of the workgroup's columns
+  // each: A = the intermediate, B = W3'^T
+  if (wave >= 8 && wave < 12) {
+    f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < 32; ks += 2) {
+      const double a0 = s_m[min(cl, 12) * kP12Pitch + 4 * ks + kq], a1 = s_m[min(cl, 12) * kP12Pitch + 4 * ks + 4 + kq];
+      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(cl < 13 ? a0 : 0.0, (double)tw[ks], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(cl < 13 ? a1 : 0.0, (double)tw[ks + 1], acc1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int row = kq + 4 * q, col = 16 * (wave - 8) + cl;
+      double v = acc0[q] + acc1[q];
+      if (row == 12) v += (double)b_tail[min(c0 + col, Fp - 1)];
+      if (row < 13) s_wc[row * 64 + col] = (float)v;
+    }
+  }
+  __syncthreads();
+
+  // phase 2: A = the slice (lane (kq, cl): row 4 s + kq, column 16 cb + cl), B = the tile's rows;
+  // lane (kq, cl) gets point cl, columns 16 cb + 4 kq + r
+  float wc[4][3];
+#pragma unroll
+  for (int cb = 0; cb < 4; cb++)
+#pragma unroll
+    for (int s = 0; s < 3; s++) wc[cb][s] = s_wc[(4 * s + kq) * 64 + 16 * cb + cl];
+  float m[4][4];
+#pragma unroll
+  for (int cb = 0; cb < 4; cb++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) m[cb][r] = -INFINITY;
+  auto tile = [&](int t, float (&xv)[3]) {
+    p12_clean(n, t, cl, xv);
+    f32x4 acc[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 3; s++)  // four independent accumulators per k step
+#pragma unroll
+      for (int cb = 0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[cb][s], xv[s], acc[cb], 0, 0, 0);
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) m[cb][r] = fmaxf(m[cb][r], acc[cb][r]);
+  };
+#pragma unroll
+  for (int i = 0; i < kP12Pre; i++)
+    if (wave + kP12Waves * i < tiles) tile(wave + kP12Waves * i, xp[i]);
+  for (int t = wave + kP12Waves * kP12Pre; t < tiles; t += kP12Waves) {
+    float xv[3];
+    p12_rows(xb, x_ld, n, t, kq, cl, xv);
+    tile(t, xv);
+  }
+  // the maximum over the 16 points of a lane row (DPP), halving the values a lane carries at every step:
+  // after xor 8, 4, 2, 1 lane cl is left with value 4 cb + r = cl of the 16, i.e. column 16 (cl >> 2) + 4 kq + (cl & 3)
+  float* mv = &m[0][0];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const bool hi = cl & 8;
+    mv[i] = fmaxf(hi ? mv[i + 8] : mv[i], xor_row<8>(hi ? mv[i] : mv[i + 8]));
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const bool hi = cl & 4;
+    mv[i] = fmaxf(hi ? mv[i + 4] : mv[i], xor_row<4>(hi ? mv[i] : mv[i + 4]));
+  }
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const bool hi = cl & 2;
+    mv[i] = fmaxf(hi ? mv[i + 2] : mv[i], xor_row<2>(hi ? mv[i] : mv[i + 2]));
+  }
+  {
+    const bool hi = cl & 1;
+    mv[0] = fmaxf(hi ? mv[1] : mv[0], xor_row<1>(hi ? mv[0] : mv[1]));
+  }
+  s_red[wave * 64 + 16 * (cl >> 2) + 4 * kq + (cl & 3)] = mv[0];
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int c = threadIdx.x;
+    float mm = s_red[c];
+#pragma unroll
+    for (int w = 1; w < kP12Waves; w++) mm = fmaxf(mm, s_red[w * 64 + c]);
+    // as pool_cols + atomic_max_f32: a column no row reached stays -inf, -0 becomes +0
+    if (c0 + c < Fp) gmax[(int64_t)b * gmax_ld + c0 + c] = mm > -INFINITY ? (mm + s_wc[12 * 64 + c]) + 0.0f : -INFINITY;
+  }
+}
+#endif
+
 // TNet(3) tail: t1[b] = fc3(h2[b]) (+ I, folded into the bias) and the t1
 // fold of conv1, W1'^T[b] = t1[b] (1 x 9) @ basis (9 x kin*nout), written
 // fragment-major with K padded to 16 (rows kin..15 zero).  One workgroup per cloud.
@@ -1816,6 +2002,18 @@ int ndnet_pn_fold_t2_run(const float* w1f, int w1_stride, const float* b1, const
       (uintptr_t)t2 % 16)
     return -20;
   k_pn_fold_t2<<<batch, 1024, 0, (hipStream_t)stream>>>(w1f, w1_stride, b1, t2, t2_ld, outf, outb);
+  return hipGetLastError() == hipSuccess ? 0 : -21;
+}
+
+int ndnet_pn_pool12_run(const float* x, int x_ld, int num_points, const float* w0f, int64_t w0_stride, const float* b0,
+                        int64_t b0_stride, const float* w_mid, const float* b_mid, const float* w_tail,
+                        const float* b_tail, int F, int Fp, float* gmax, int gmax_ld, int batch, void* stream) {
+  if (!x || !w0f || !b0 || !w_mid || !b_mid || !w_tail || !b_tail || !gmax || batch <= 0 || batch > 65535 ||
+      num_points <= 0 || x_ld < 12 || x_ld % 4 || w0_stride < 1024 || b0_stride < 64 || F <= 0 || F > Fp ||
+      (Fp != 32 && Fp % 64) || gmax_ld < Fp)
+    return -20;
+  k_pn_pool12<<<dim3((Fp + 63) / 64, batch), kP12Waves * 64, 0, (hipStream_t)stream>>>(
+      x, x_ld, num_points, w0f, w0_stride, b0, b0_stride, w_mid, b_mid, w_tail, b_tail, Fp, gmax, gmax_ld);
   return hipGetLastError() == hipSuccess ? 0 : -21;
 }
 

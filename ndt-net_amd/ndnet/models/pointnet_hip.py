@@ -10,6 +10,8 @@ with small per-cloud steps between them:
      TNet(64):  -> 64 -> 64 -> 128 -> 1024, max                  -> g2
      FC head (1024 -> 512 -> 256 -> 4096) + I                    -> t2
   C  conv2 with t2^T folded in (x_t2 = t2^T x1), conv3, max      -> g3 [F]
+     (no ReLU in it: in the x6 / fp32 modes one per-cloud 12 -> F layer,
+     ``ndnet_pn_pool12_run``, in the chain's place; ``BACKBONE``)
   D  seg conv1 split: W[:, :64] t2^T x1 per point + (W[:, 64:] g3 + b) per
      cloud (the reference concatenates the broadcast g3 to every point:
      ndtnet.py:227-230), -> 512 -> 256 -> 128 -> C+1, log_softmax
@@ -554,7 +556,36 @@ def _use_t32(B: int, n: int, device) -> bool:
     return 2 * B * ((n + 63) // 64) <= _cus[device]
 
 
-def _run_chain(ch: "_Chain", x: torch.Tensor, out=None) -> None:
+class _Pool12:
+    """Argument block of one ``ndnet_pn_pool12_run``: chain C as a per-cloud
+    12 -> F layer (include/ndnet_pointnet.h).  It keeps the tensors alive and
+    reads their addresses once, as ``_build_chain`` does; the kernel reads
+    their contents at every launch, so an in-place re-fold is followed."""
+
+    def __init__(self, ws: "_Workspace") -> None:
+        W = ws.W
+        (w_mid, b_mid), (w_tail, b_tail) = W.C_mid, W.C_tail
+        assert w_mid.shape == (64, 128) and w_mid.is_contiguous() and w_tail.shape[0] == 128 and w_tail.is_contiguous()
+        self.tensors = (ws.w1t2f, ws.b1t2, w_mid, b_mid, w_tail, b_tail, ws.g3)
+        self.n, self.F, self.Fp = ws.N, W.F, w_tail.shape[1]
+        self.args = (ws.w1t2f.data_ptr(), ws.w1t2f.stride(0), ws.b1t2.data_ptr(), ws.b1t2.stride(0),
+                     w_mid.data_ptr(), b_mid.data_ptr(), w_tail.data_ptr(), b_tail.data_ptr(), self.F, self.Fp,
+                     ws.g3.data_ptr(), ws.g3.stride(0))
+
+
+def _run_pool12(blk: "_Pool12", x: torch.Tensor) -> None:
+    B, n, _ = x.shape
+    assert n == blk.n and x.stride(2) == 1 and x.stride(0) == n * x.stride(1) and x.dtype == torch.float32
+    rc = _lib.lib().ndnet_pn_pool12_run(x.data_ptr(), x.stride(1), n, *blk.args, B, _lib.stream_ptr(x.device))
+    _lib.check(rc, "ndnet_pn_pool12_run")
+
+
+def _run_chain(ch, x: torch.Tensor, out=None) -> None:
+    """One per-point launch of the forward: a fused chain (``_Chain``), or
+    chain C's 12 -> F form (``_Pool12``)."""
+    if isinstance(ch, _Pool12):
+        _run_pool12(ch, x)
+        return
     assert x.stride(1) == ch.x_ld and x.stride(2) == 1 and x.dtype == torch.float32
     ch.x = x.data_ptr()
     ch.out = out.data_ptr() if out is not None else None
@@ -627,6 +658,16 @@ class _Workspace:
                                dict(out_cols=W.C1, fuse=(1,))))
         self.N = N
         self.structs = {}
+        self.pool12 = None  # chain C's 12 -> F argument block (``uses_pool12``), built at its first launch
+
+    def uses_pool12(self) -> bool:
+        """Whether chain C runs as one ``ndnet_pn_pool12_run`` in the current mode.
+        Only where the layers are fp32-accurate ("x6", "fp32": the reduced modes
+        are defined layer by layer and keep the chain), conv1 has per-cloud
+        weights that ``ndnet_pn_fold_t2_run`` has already folded t2 into (not the
+        baseline; not NDNET_PN_FOLD_T2=chain, where chain C's prologue is what
+        publishes them for chain D), and NDNET_PN_BACKBONE is not "chain"."""
+        return BACKBONE == "pool12" and FOLD_T2_KERNEL and not self.W.baseline and self.mode in ("x6", "fp32")
 
     def hip_layers(self, mode: str) -> list:
         """The chains' layers (A-D; A-C for a classification model) for ``_build_chain`` in one precision mode:
@@ -684,14 +725,19 @@ class _Workspace:
                 cc = structs[2]
                 cc.fold_t2, cc.fold_ld = self.t2.data_ptr(), self.t2.stride(0)
                 cc.fold_out_w, cc.fold_out_b = self.w1t2f.data_ptr(), self.b1t2.data_ptr()
+        blk = structs[i]
+        if i == 2 and self.uses_pool12():  # chain C collapsed to its 12 -> F layer: one launch in the chain's place
+            if self.pool12 is None:
+                self.pool12 = _Pool12(self)
+            blk = self.pool12
         if chain_timing is not None:  # torch events on the launch stream (bench.py)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            _run_chain(structs[i], x, out)
+            _run_chain(blk, x, out)
             e1.record()
             chain_timing.append((i, e0, e1))
         else:
-            _run_chain(structs[i], x, out)
+            _run_chain(blk, x, out)
 
 
 def _folded(model):
@@ -721,6 +767,14 @@ def _folded(model):
 # (default, round 5) once per cloud by ndnet_pn_fold_t2_run after fc3; "chain"
 # in chain C's prologue, every workgroup (fold_t2), published for chain D
 FOLD_T2_KERNEL = os.environ.get("NDNET_PN_FOLD_T2", "kernel") == "kernel"
+# Chain C (conv1 with t1 and t2 folded, conv2, conv3, max: no ReLU anywhere):
+# "pool12" (default) runs it as one per-cloud 12 -> F layer, ndnet_pn_pool12_run
+# (9,216 fp32 multiply-adds per point at F = 768 where the layered chain does
+# 106,496 split-bf16 ones), wherever ``_Workspace.uses_pool12`` allows; "chain"
+# keeps the layered k_pn_chain launch everywhere (A/B runs)
+BACKBONE = os.environ.get("NDNET_PN_BACKBONE", "pool12")
+if BACKBONE not in ("pool12", "chain"):
+    raise ValueError(f"NDNET_PN_BACKBONE must be 'pool12' or 'chain', not {BACKBONE!r}")
 # TNet(3)'s tail (fc3 + the t1 fold of conv1): "chain" (default) computes it in
 # chain B's prologue, per workgroup (ndnet_pn_chain.head_*: one launch and one
 # boundary fewer); "kernel" runs ndnet_pn_head3_run before chain B
