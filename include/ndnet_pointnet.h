@@ -106,6 +106,38 @@ typedef struct ndnet_pn_chain {
   // so a later chain runs the same transformed layer 0 as a plain per-cloud layer (chain D)
   float* fold_out_w;
   float* fold_out_b;
+  // Fields added after the first release of this struct; zero means the behaviour above.
+  //
+  // head_h2 and fold_t2 may both be set (chain B with TNet(64)'s first layer collapsed into conv1): the
+  // head prologue runs first and leaves W1f[b] (conv1 with t1 folded) as layer 0's weights, then the fold
+  // prologue replaces them by W1f[b] fold_t2[b] -- so with no ReLU between conv1 and the folded layer,
+  // layer 0 IS the pair, relu(x (W1f[b] M) + (b1 M + bM)) with L[0].relu = 1.  What the head prologue
+  // publishes to L[0].w is still the plain W1f[b] (ndnet_pn_fold_t2_run and ndnet_pn_pool12_run read it),
+  // bit for bit what it publishes alone.  The matrix is then loaded with the kernel's first loads, behind
+  // the head prologue's round trips.
+  // fold_ld == 0: one matrix shared by all clouds (else fold_ld >= 4096, one per cloud).
+  // fold_bias: optional (NULL: none), [64], shared: the folded layer's own bias, added to b0' = b0^T M
+  // (and to what fold_out_b receives).  NDNET_ERR_ARG with fold_bias set and fold_t2 NULL.
+  // Nothing of the product is kept between launches: it is formed from the tensors as they are at the
+  // launch, so an in-place re-fold of either factor is followed.
+  const float* fold_bias;
+  // 1: a NaN or an infinity among an input row's in_cols values enters layer 0 as NaN, whichever way
+  // layer 0 runs (on the VALU, from the staged input tile, as the direct fused pair below);
+  // NDNET_ERR_ARG for any value but 0 and 1.  With L[0].relu the row then
+  // leaves layer 0 as zeros -- what the layered pair gives for it: conv1 (no ReLU) hands an infinity or
+  // a NaN to the split-bf16 layer behind it, whose plane split (inf - inf) makes every output of that
+  // row NaN, and its ReLU's maximum drops the NaN.  A collapsed first layer sets this flag to keep
+  // that.  (Finite rows whose 64-wide conv1 output overflows fp32 although the composed layer's does
+  // not are out of scope: there the two forms differ.)
+  int32_t x_nonfinite_nan;
+  int32_t reserved0;
+  // A chain may open with a fused pair whose P is a prec-0 layer with K = 16 (chain D with the seg
+  // head's conv1 collapsed into its first layer: P = 12 -> 512 per cloud, ReLU, fuse_next, into
+  // Q = 512 -> 256 split-bf16).  The 16-wave 64-point build runs it without an input tile when
+  // Q.N == 256, Q.prec != 0, x_ld % 4 == 0, x is 16-byte aligned and head_h2 is NULL: every wave keeps
+  // its 16 rows' input pieces in registers as P's operand for all chunks, and P's weights stream one
+  // 1 KB fp32 fragment per wave and chunk.  Every other such block, and ndnet_pn_chain_run_t32, stage
+  // the tile and run the generic fused pair.
 } ndnet_pn_chain;
 
 /* Runs one chain over `batch` clouds on `stream` (a hipStream_t; NULL = default
@@ -150,6 +182,13 @@ int ndnet_pn_fc_run(const float *in, int ld_in, const float *W, const float *bia
  * workgroups, each summing its waves' K-slices in a fixed order. */
 int ndnet_pn_fc_mfma_run(const float *in, int ld_in, const float *Wf, const float *bias, float *out, int ld_out,
                          int batch, int K, int N, int relu, void *stream);
+/* The same with a bias row per cloud: out[b][n] = act(bias[b * bias_ld + n] + ...), bias_ld >= N, or
+ * bias_ld == 0 for one shared row -- then it is ndnet_pn_fc_mfma_run, bit for bit (that entry forwards
+ * here).  The seg head's per-cloud bias with conv1 collapsed into chain D's first layer:
+ * cvec[b] = g3[b] s1g^T + bd[b] (ndnet_pn_fold_seg_run).  NDNET_ERR_ARG (-20) as ndnet_pn_fc_mfma_run,
+ * and for 0 < bias_ld < N. */
+int ndnet_pn_fc_mfma_bias_run(const float *in, int ld_in, const float *Wf, const float *bias, int bias_ld, float *out,
+                              int ld_out, int batch, int K, int N, int relu, void *stream);
 /* The classification head's last layer and softmax (ndtnet.py:188-194: conv3
  * then softmax over the classes; no BatchNorm) in one launch, for any batch:
  *   probs[b][c] = softmax_c(bias[c] + sum_k in[b][k] W^T[k][c]),  c < out_cols
@@ -232,6 +271,29 @@ int ndnet_pn_head3_run(const float *h2, int ld_h, const float *W3, const float *
  * aligned), outf [batch][1024], outb [batch][64]. */
 int ndnet_pn_fold_t2_run(const float *w1f, int w1_stride, const float *b1, const float *t2, int t2_ld, float *outf,
                          float *outb, int batch, void *stream);
+
+/* ndnet_pn_fold_t2_run and, in the same launch, the seg head's conv1 collapsed into chain D's first
+ * layer.  x_t2 = x W1''[b] + b1''[b] (outf, outb) feeds the seg head's conv1[:, :64] with no ReLU between
+ * (ndtnet.py:152-157, :227-233), so the two are one per-cloud 12 -> N2 layer:
+ *   wd[b] = W1''[b] s1aT      (12 x N2) in the fragment-major K = 16 layout, 16 * N2 floats per cloud;
+ *                             rows 12..15 are left untouched: zero-initialise them
+ *   bd[b] = b1''[b] s1aT + s1b   (N2 floats; the per-cloud global-feature term is added by
+ *                             ndnet_pn_fc_mfma_bias_run)
+ * from the fp32 values of W1''[b], b1''[b] just written, the products accumulated in double (i
+ * ascending) and rounded once to fp32.  outf and outb are written exactly as ndnet_pn_fold_t2_run
+ * writes them, bit for bit (ndnet_pn_pool12_run reads them).  Nothing is cached: every launch reads
+ * the tensors as they are, so an in-place re-fold is followed.
+ *   w1f, w1_stride, b1, t2, t2_ld, outf, outb   as ndnet_pn_fold_t2_run
+ *   s1aT   [64][N2] row-major (the seg head's conv1[:, :64]^T, BatchNorm folded), 16-byte aligned
+ *   s1b    [N2];  N2 a multiple of 64
+ *   wd     [batch][wd_stride >= 16 * N2];  bd [batch][bd_stride >= N2]
+ * One launch of (N2 / 64, batch) workgroups for any batch in 1..65535; bit-identical from run to run.
+ * NDNET_ERR_ARG (-20) before any launch for a NULL pointer, batch outside 1..65535, a stride below
+ * its minimum, t2_ld % 4, N2 < 1 or N2 % 64, or t2 / s1aT not 16-byte aligned; -21 on a launch
+ * failure.  No allocation, no synchronisation: graph-capturable. */
+int ndnet_pn_fold_seg_run(const float *w1f, int w1_stride, const float *b1, const float *t2, int t2_ld, float *outf,
+                          float *outb, const float *s1aT, const float *s1b, int N2, float *wd, int64_t wd_stride,
+                          float *bd, int64_t bd_stride, int batch, void *stream);
 
 /* Chain C (conv1 with t1 and t2 folded, conv2, conv3, max over points) as one
  * per-cloud 12 -> F layer: no ReLU separates the three (ndtnet.py:149-161),

@@ -778,10 +778,18 @@ __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx&
 // 2 k-groups, 3 planes each: 48 VGPRs) are loaded one chunk ahead, right after
 // the previous chunk's MFMAs consumed the registers, so each load has a whole
 // phase and a barrier to arrive.  Same products, same accumulation order.
-template <int RB, int T>
+//
+// PF32: P is a prec-0 layer with K = 16 at the head of the chain (the seg head's conv1 with conv1, t1 and
+// t2 folded in per cloud: 12 -> 512).  Its A operand is this lane's piece of its input row (xa: row
+// prow0 + cl, columns 4 kq .. 4 kq + 3, loaded once by the kernel's prologue and kept for all chunks),
+// its weights per chunk one fp32 fragment (1 KB per wave, loaded one chunk ahead as wp is): four
+// v_mfma_f32_16x16x4_f32 where the split-bf16 P issues twelve bf16 MFMAs and six LDS fragment reads.
+// There is no LDS input tile and no layer-0 phase in front of it.  Q's side is the same code.
+template <int RB, int T, bool PF32 = false>
 __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const LayerCtx& P, const LayerCtx& Q, int in,
                                                                      int fbuf, int out, int pout, float* gmax,
-                                                                     int rows_valid, bool out_planes) {
+                                                                     int rows_valid, bool out_planes,
+                                                                     f32x4 xa = {0.f, 0.f, 0.f, 0.f}) {
   constexpr int WR = kRowBlocks / RB, WC = kWaves / WR;  // Q: NB = 1
   constexpr int PWC = kWaves / kRowBlocks;                // P: 4 column groups of one block
   static_assert(PWC == 4 && kFuseNC == 64, "16 waves, 64-column chunks");
@@ -797,7 +805,12 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
   // chunk f's weights: P column block 4 f + pwc, k-groups 0, 1; Q column block qwc, k-groups 2 f, 2 f + 1
   constexpr int NPL = kPlanes<T>;  // of the three planes stored per k-group
   bf16x8 wp[2][1][NPL], wq[2][1][NPL];
+  f32x4 wpf[1];  // PF32: chunk f's fragment of P (one k-group)
   auto load_p = [&](int f) {
+    if constexpr (PF32) {
+      wpf[0] = P.w[(int64_t)(4 * f + pwc) * 64];
+      return;
+    }
     const bf16x8* s = P.w6 + ((int64_t)(4 * f + pwc) * P.KG) * 3 * 64;
 #pragma unroll
     for (int k = 0; k < 2; k++)
@@ -814,8 +827,13 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
   auto p_chunk = [&](int f) {
     f32x4 acc1[1][1];
     zero_acc(acc1);
+    if constexpr (PF32) {
+      const f32x4 a1[1] = {xa};
+      mma_kgroup<1, 1>(acc1, a1, wpf);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 2; k++) mma_kgroup_x6<1, 1, T>(acc1, ain6 + 32 * k, kP * pinb, 16 * pinb, wp[k]);
+      for (int k = 0; k < 2; k++) mma_kgroup_x6<1, 1, T>(acc1, ain6 + 32 * k, kP * pinb, 16 * pinb, wp[k]);
+    }
     store_cols_planes<1, 1, T>(acc1, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fbuf + (f & 1) * fbsz, fpb, 16 * pwc);
   };
   f32x4 acc2[RB][1];
@@ -920,6 +938,20 @@ __host__ __device__ inline bool valu_layer0(const ndnet_pn_chain& A) {
          A.in_cols <= 12 && A.x_ld % 4 == 0;
 }
 
+// 1: the 16-wave 64-point build runs a fused pair into a 256-wide split-bf16 Q software-pipelined
+// (fused_pair_x6p); 0 (a build switch for comparisons): every pair takes the generic fused_pair.
+#ifndef NDNET_PN_FUSED_PIPE
+#define NDNET_PN_FUSED_PIPE 1
+#endif
+
+// The chain opens with a fused pair whose P (prec 0, K = 16) the 16-wave 64-point build runs straight
+// from the input rows (fused_pair_x6p<.., PF32>): no input tile is staged and none is sized.
+__host__ __device__ inline bool pair0_direct(const ndnet_pn_chain& A) {
+  return kP == 64 && kWaves == 16 && NDNET_PN_FUSED_PIPE && A.num_layers >= 2 && A.L[0].fuse_next &&
+         A.L[0].prec == 0 && A.L[0].K == 16 && A.L[1].prec != 0 && A.L[1].N == 256 && A.x_ld % 4 == 0 &&
+         (uintptr_t)A.x % 16 == 0 && !A.head_h2;
+}
+
 // LDS floats of the VALU layer-0 prologue scratch (W0^T [16][64] + bias [64]),
 // overlaid on activation region 0, which layer 0 neither reads nor writes.
 constexpr int kValu0Floats = 16 * 64 + 64;
@@ -980,6 +1012,35 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
   static_assert(kV0Pass >= 1 && kV0Pass * kThreads == kP * 16, "whole layer-0 passes");
   const int vq = threadIdx.x & 15;
   f32x4 xin[kV0Pass][3] = {};
+  // both prologues (chain B collapsed): the fold matrix is no product of this launch's head, so waves
+  // 0..3, which run the fold, load their B operands of its 16 MFMA steps here with the kernel's first
+  // loads -- M[4 st + fk][16 wave + fr], no LDS staging -- and they land under the head prologue's two
+  // round trips
+  const bool fold_early = A.head_h2 && A.fold_t2;
+  constexpr int kFoldPitch = 68;  // floats per row of the head's W1f copy the fold reads: 16 rows x 4 k on 64 distinct banks
+  float fmr[16] = {};
+  if (fold_early && wave < 4) {
+    const float* mb = A.fold_t2 + (int64_t)b * A.fold_ld + (lane >> 4) * 64 + 16 * wave + (lane & 15);
+#pragma unroll
+    for (int st = 0; st < 16; st++) fmr[st] = mb[st * 256];
+  }
+  // ... and the folded layer's own bias (TNet(64) conv1's), joined to b0' by waves 0..3: column 16 wave + (lane & 15)
+  const float fb = A.fold_bias ? A.fold_bias[(16 * wave + (lane & 15)) & 63] : 0.0f;
+  // a chain that opens with the direct fused pair: this lane's piece of its input row, P's A operand for
+  // every chunk (row (wave / 4) * 16 + cl, columns 4 kq ..; zero past in_cols and past the cloud)
+  const bool direct0 = pair0_direct(A);
+  f32x4 xa = {0.f, 0.f, 0.f, 0.f};
+  if (direct0) {
+    const int kq = lane >> 4, p = p0 + (wave / 4) * 16 + (lane & 15);
+    if (p < A.num_points && 4 * kq < A.in_cols) {
+      xa = *reinterpret_cast<const f32x4*>(A.x + ((int64_t)b * A.num_points + p) * A.x_ld + 4 * kq);
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        if (4 * kq + s >= A.in_cols) xa[s] = 0.0f;
+        else if (A.x_nonfinite_nan && !(fabsf(xa[s]) < INFINITY)) xa[s] = NAN;
+      }
+    }
+  }
   if (v0) {
 #pragma unroll
     for (int ps = 0; ps < kV0Pass; ps++) {
@@ -1044,7 +1105,10 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
         for (int a = 0; a < 9; a++) acc += s_t1[a] * A.head_basis[a * M + k * A.head_nout + n];
       }
       if (publish) w1[e] = acc;
-      if (v0) s_w0[k * 64 + n] = acc;
+      // the fold prologue follows: its A operand [W1f; b1; 0] goes to region 1 at a pitch its reads do
+      // not conflict on, and s_w0 is left to its output (no barrier between its MFMAs and its stores)
+      if (fold_early) g_smem[reg[1] + k * kFoldPitch + n] = k == 12 ? g_smem[boff[0] + n] : acc;
+      else if (v0) s_w0[k * 64 + n] = acc;
     }
     // !v0: layer 0 reads these weights back: __syncthreads' workgroup-scope release
     // / acquire orders this workgroup's stores before its loads (same CU; no
@@ -1060,24 +1124,37 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
     // GEMM (rows 0..11 W0^T, row 12 the bias, 13..15 zero) on the fp32 MFMA,
     // waves 0..3 one 16-column block each, t2 staged in region 1 (layer 0 has
     // not written it yet; the launcher keeps the biases past it)
+    // After the head prologue (chain B collapsed: a shared matrix, hot in L2) the same product takes
+    // its B operand from registers (fmr) and its A operand from the head's copy in region 1, so the
+    // fold costs one barrier and 16 MFMAs of four waves.
     float* const s_t2 = g_smem + reg[1];
-    const f32x4* t2b = reinterpret_cast<const f32x4*>(A.fold_t2 + (int64_t)b * A.fold_ld);
-    for (int e = threadIdx.x; e < 1024; e += kThreads) reinterpret_cast<f32x4*>(s_t2)[e] = t2b[e];
-    __syncthreads();  // + s_w0 (W0^T row-major) and layer 0's bias at boff[0]
     f32x4 fo = {0.f, 0.f, 0.f, 0.f};
     const int fr = lane & 15, fk = lane >> 4;  // operand row / k within a 4-step
-    if (wave < 4) {
+    if (fold_early) {
+      __syncthreads();  // [W1f; b1; 0] at s_t2, pitch kFoldPitch
+      if (wave < 4) {
 #pragma unroll
-      for (int st = 0; st < 16; st++) {
-        const int i = 4 * st + fk;
-        const float av = fr < 12 ? s_w0[fr * 64 + i] : fr == 12 ? g_smem[boff[0] + i] : 0.0f;
-        const float bv = s_t2[i * 64 + 16 * wave + fr];
-        fo = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, fo, 0, 0, 0);
+        for (int st = 0; st < 16; st++)
+          fo = __builtin_amdgcn_mfma_f32_16x16x4f32(s_t2[fr * kFoldPitch + 4 * st + fk], fmr[st], fo, 0, 0, 0);
       }
+    } else {
+      const f32x4* t2b = reinterpret_cast<const f32x4*>(A.fold_t2 + (int64_t)b * A.fold_ld);
+      for (int e = threadIdx.x; e < 1024; e += kThreads) reinterpret_cast<f32x4*>(s_t2)[e] = t2b[e];
+      __syncthreads();  // + s_w0 (W0^T row-major) and layer 0's bias at boff[0]
+      if (wave < 4) {
+#pragma unroll
+        for (int st = 0; st < 16; st++) {
+          const int i = 4 * st + fk;
+          const float av = fr < 12 ? s_w0[fr * 64 + i] : fr == 12 ? g_smem[boff[0] + i] : 0.0f;
+          const float bv = s_t2[i * 64 + 16 * wave + fr];
+          fo = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, fo, 0, 0, 0);
+        }
+      }
+      __syncthreads();
     }
-    __syncthreads();
     if (wave < 4) {  // lane (fk, fr): rows 4 fk + r, column 16 wave + fr
       const int n = 16 * wave + fr;
+      if (A.fold_bias && fk == 3) fo[0] += fb;  // row 12: b0' = b0^T M + the folded layer's bias
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int row = 4 * fk + r;
@@ -1106,8 +1183,12 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
     for (int ps = 0; ps < kV0Pass; ps++) {
       const int vr = (threadIdx.x >> 4) + ps * (kThreads / 16);
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const float xs[12] = {xin[ps][0][0], xin[ps][0][1], xin[ps][0][2], xin[ps][0][3], xin[ps][1][0], xin[ps][1][1],
-                            xin[ps][1][2], xin[ps][1][3], xin[ps][2][0], xin[ps][2][1], xin[ps][2][2], xin[ps][2][3]};
+      float xs[12] = {xin[ps][0][0], xin[ps][0][1], xin[ps][0][2], xin[ps][0][3], xin[ps][1][0], xin[ps][1][1],
+                      xin[ps][1][2], xin[ps][1][3], xin[ps][2][0], xin[ps][2][1], xin[ps][2][2], xin[ps][2][3]};
+      if (A.x_nonfinite_nan) {  // a collapsed first layer: the row leaves its ReLU as zeros, as the layered pair's does
+#pragma unroll
+        for (int k = 0; k < 12; k++) xs[k] = fabsf(xs[k]) < INFINITY ? xs[k] : NAN;
+      }
 #pragma unroll
       for (int k = 0; k < 12; k++) {
         if (k < A.in_cols) {
@@ -1143,13 +1224,14 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
         *reinterpret_cast<f32x4*>(g_smem + out + vr * pitch1 + 4 * vq) = acc;
       }
     }
-  } else {
+  } else if (!direct0) {
     const int K0 = A.L[0].K;
     for (int e = threadIdx.x; e < kP * K0; e += kThreads) {
       const int r = e / K0, c = e % K0;
       const int p = p0 + r;
       float v = 0.0f;
       if (p < A.num_points && c < A.in_cols) v = A.x[((int64_t)b * A.num_points + p) * A.x_ld + c];
+      if (A.x_nonfinite_nan && !(fabsf(v) < INFINITY)) v = NAN;
       g_smem[r * pitch0 + c] = v;
     }
   }
@@ -1157,7 +1239,19 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
   PN_STAMP(2);
   const int rows_valid = A.num_points - p0;
   float* const gmax_b = A.mode == 0 ? A.gmax + (int64_t)b * A.gmax_ld : nullptr;
-  for (int l = v0 ? 1 : 0; l < A.num_layers; l++) {
+  int lfirst = v0 ? 1 : 0;
+  if constexpr (kP == 64 && kWaves == 16) {
+    if (direct0) {  // layers 0 and 1 as the direct fused pair, ahead of the loop: xa is live up to here only
+      const LayerCtx P = layer_ctx(A, 0, b, g_smem + boff[0]), Q = layer_ctx(A, 1, b, g_smem + boff[1]);
+      const bool last = A.num_layers == 2;
+      fused_pair_x6p<4, T, true>(P, Q, reg[0], fbuf, reg[0], pitch0, (last && gmax_b) ? gmax_b : nullptr, rows_valid,
+                                 !last && A.L[2].prec, xa);
+      __syncthreads();
+      PN_STAMP(3 + 1);
+      lfirst = 2;
+    }
+  }
+  for (int l = lfirst; l < A.num_layers; l++) {
     const int in = reg[l & 1], pin = (l & 1) ? pitch1 : pitch0;
     if (A.L[l].fuse_next) {  // layers l and l + 1 together; l + 1 writes region (l + 2) & 1
       const LayerCtx P = layer_ctx(A, l, b, g_smem + boff[l]), Q = layer_ctx(A, l + 1, b, g_smem + boff[l + 1]);
@@ -1171,9 +1265,6 @@ __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int pla
         if (Q.N == 256) fused_pair<2, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
         else fused_pair<1, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
       } else {
-#ifndef NDNET_PN_FUSED_PIPE
-#define NDNET_PN_FUSED_PIPE 1
-#endif
         bool piped = false;
         if constexpr (kWaves == 16) {
           if (NDNET_PN_FUSED_PIPE && Q.N == 256 && P.prec && Q.prec && P.KG == 2) {
@@ -1331,8 +1422,9 @@ constexpr int kFcWaves = NDNET_PN_FC_WAVES, kFcMaxG = 64 / kFcWaves;  // K <= 16
 template <int CBW>
 __global__ void __launch_bounds__(kFcWaves * 64) k_pn_fc_mfma(const float* __restrict__ in, int ld_in,
                                                               const f32x4* __restrict__ wf,
-                                                              const float* __restrict__ bias, float* __restrict__ out,
-                                                              int ld_out, int B, int KG, int relu) {
+                                                              const float* __restrict__ bias, int bias_ld,
+                                                              float* __restrict__ out, int ld_out, int B, int KG,
+                                                              int relu) {
   constexpr int kG = kFcMaxG / CBW;
   static_assert(CBW <= kFcWaves && kG >= 1, "one reducing wave per column block");
   __shared__ f32x4 part[kFcWaves][CBW][64];
@@ -1341,6 +1433,13 @@ __global__ void __launch_bounds__(kFcWaves * 64) k_pn_fc_mfma(const float* __res
   const int cb0 = blockIdx.x * CBW;
   const int kg0 = KG * wave / kFcWaves, ng = KG * (wave + 1) / kFcWaves - kg0;
   const float* xr = in + (int64_t)(cl < B ? cl : 0) * ld_in + 16 * kg0 + 4 * kq;  // rows past B: discarded
+  // the reducing waves' bias values (clouds 4 kq + r of column 16 (cb0 + wave) + cl; rows past B: the last
+  // row's, discarded), loaded with the first loads; bias_ld 0: one bias row for every cloud
+  float bv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (wave < CBW) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) bv[r] = bias[(int64_t)min(4 * kq + r, B - 1) * bias_ld + 16 * (cb0 + wave) + cl];
+  }
   f32x4 wv[CBW][kG], xv[kG];
 #pragma unroll
   for (int i = 0; i < kG; i++) {
@@ -1368,12 +1467,11 @@ __global__ void __launch_bounds__(kFcWaves * 64) k_pn_fc_mfma(const float* __res
   for (int w = 1; w < kFcWaves; w++) t += part[w][j][lane];
   // lane (kq, cl): clouds 4 kq + r of column 16 (cb0 + j) + cl
   const int n = 16 * (cb0 + j) + cl;
-  const float bv = bias[n];
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     const int b = 4 * kq + r;
     if (b < B) {
-      float v = t[r] + bv;
+      float v = t[r] + bv[r];
       if (relu) v = fmaxf(v, 0.0f);
       out[(int64_t)b * ld_out + n] = v;
     }
@@ -1560,6 +1658,65 @@ __global__ void __launch_bounds__(1024) k_pn_fold_t2(const float* __restrict__ w
     for (int i = 0; i < 64; i++) acc = fmaf(s_w[r * 64 + i], s_t[i * 64 + n], acc);
     if (r < 12) outf[(int64_t)b * 1024 + ((((n >> 4) * 64 + ((r >> 2) & 3) * 16 + (n & 15)) << 2) + (r & 3))] = acc;
     else outb[(int64_t)b * 64 + n] = acc;
+  }
+}
+
+// k_pn_fold_t2's work and, from the values it has just formed, the seg head's conv1 collapsed into the same
+// per-cloud layer (ndnet_pn_fold_seg_run): no ReLU separates x_t2 = x W1''[b] + b1''[b] from conv1's
+// x_t2 s1a^T (+ the per-cloud global-feature bias), so chain D's first layer is 12 -> N2,
+//   wd[b] = W1''[b] s1a^T (12 x N2, fragment-major K = 16, rows 12..15 untouched),  bd[b] = b1''[b] s1a^T + s1b.
+// One workgroup per 64 columns of one cloud.  Each repeats the 13 x 64 fold (the same fp32 FMAs in the
+// same order as k_pn_fold_t2: the cloud's first workgroup stores outf / outb, bit for bit that kernel's),
+// then forms its 13 x 64 slice from those fp32 values, one output per thread: double FMAs, i ascending,
+// rounded once, both operands converted to double once when they are staged in LDS.  On the VALU, not the
+// f64 MFMA: this launch runs in the forward's serial chain beside other forwards' chain kernels, which
+// keep the matrix pipe busy (a 256-column form on v_mfma_f64_16x16x4_f64 measured 12 us in the pipelined
+// step where k_pn_fold_t2 takes 5.4).  Nothing is kept between launches.
+__global__ void __launch_bounds__(1024) k_pn_fold_seg(const float* __restrict__ w1f, int w1_stride,
+                                                      const float* __restrict__ b1, const float* __restrict__ t2,
+                                                      int t2_ld, float* __restrict__ outf, float* __restrict__ outb,
+                                                      const float* __restrict__ s1aT, const float* __restrict__ s1b,
+                                                      int N2, float* __restrict__ wd, int64_t wd_stride,
+                                                      float* __restrict__ bd, int64_t bd_stride) {
+  const int b = blockIdx.y, c0 = 64 * blockIdx.x, e = threadIdx.x;
+  __shared__ float s_w[13 * 64];   // rows 0..11 W1'^T (row-major [k][n]), row 12 the bias
+  __shared__ float s_t[64 * 64];
+  __shared__ double s_s[64 * 64];  // s1a^T[i][c0 + c]
+  __shared__ double s_o[13 * 64];  // [W1''; b1''] as stored (fp32 values)
+  const int r = e >> 6, n = e & 63;
+  const float sb = e < 13 * 64 ? s1b[c0 + n] : 0.0f;
+  {
+    const float* wb = w1f + (int64_t)b * w1_stride;
+    {  // fragment-major element e -> (k, n)
+      const int cb = e >> 8, ln = (e >> 2) & 63, k = 4 * (ln >> 4) + (e & 3), nn = 16 * cb + (ln & 15);
+      const float v = wb[e];
+      if (k < 12) s_w[k * 64 + nn] = v;
+    }
+    if (e < 64) s_w[12 * 64 + e] = b1[e];
+    reinterpret_cast<f32x4*>(s_t)[e] = reinterpret_cast<const f32x4*>(t2 + (int64_t)b * t2_ld)[e];
+    const f32x4 sv = *reinterpret_cast<const f32x4*>(s1aT + (int64_t)(e >> 4) * N2 + c0 + 4 * (e & 15));
+#pragma unroll
+    for (int j = 0; j < 4; j++) s_s[4 * e + j] = (double)sv[j];
+  }
+  __syncthreads();
+  if (e < 13 * 64) {
+    float acc = 0.0f;
+#pragma unroll 16
+    for (int i = 0; i < 64; i++) acc = fmaf(s_w[r * 64 + i], s_t[i * 64 + n], acc);
+    s_o[e] = (double)acc;
+    if (blockIdx.x == 0) {
+      if (r < 12) outf[(int64_t)b * 1024 + ((((n >> 4) * 64 + ((r >> 2) & 3) * 16 + (n & 15)) << 2) + (r & 3))] = acc;
+      else outb[(int64_t)b * 64 + n] = acc;
+    }
+  }
+  __syncthreads();
+  if (e < 13 * 64) {
+    double acc = 0.0;
+#pragma unroll 16
+    for (int i = 0; i < 64; i++) acc = fma(s_o[r * 64 + i], s_s[i * 64 + n], acc);
+    const int col = c0 + n;
+    if (r < 12) wd[(int64_t)b * wd_stride + ((((col >> 4) * 64 + ((r >> 2) & 3) * 16 + (col & 15)) << 2) + (r & 3))] = (float)acc;
+    else bd[(int64_t)b * bd_stride + col] = (float)(acc + (double)sb);
   }
 }
 
@@ -1939,10 +2096,11 @@ int fc_mfma_cbw(int nb, int ngmax) {
 extern "C" {
 
 #if NDNET_PN_TILE == 64  // the 32-point build exports only its chain entry point (below)
-int ndnet_pn_fc_mfma_run(const float* in, int ld_in, const float* Wf, const float* bias, float* out, int ld_out,
-                         int batch, int K, int N, int relu, void* stream) {
+int ndnet_pn_fc_mfma_bias_run(const float* in, int ld_in, const float* Wf, const float* bias, int bias_ld, float* out,
+                              int ld_out, int batch, int K, int N, int relu, void* stream) {
   if (!in || !Wf || !bias || !out || batch <= 0 || batch > 16 || K <= 0 || K % 16 || K > 16 * kFcWaves * kFcMaxG ||
-      N <= 0 || N % 16 || ld_in % 4 || ld_in < K || ld_out < N || ((uintptr_t)in | (uintptr_t)Wf) % 16)
+      N <= 0 || N % 16 || ld_in % 4 || ld_in < K || ld_out < N || ((uintptr_t)in | (uintptr_t)Wf) % 16 ||
+      (bias_ld != 0 && bias_ld < N))
     return -20;
   const int KG = K / 16, nb = N / 16, ngmax = (KG + kFcWaves - 1) / kFcWaves;
   // column blocks per workgroup: 4 while that keeps >= 32 workgroups and the
@@ -1951,12 +2109,17 @@ int ndnet_pn_fc_mfma_run(const float* in, int ld_in, const float* Wf, const floa
   const f32x4* wf = reinterpret_cast<const f32x4*>(Wf);
   hipStream_t st = (hipStream_t)stream;
   if (cbw == 4)
-    k_pn_fc_mfma<4><<<nb / 4, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, out, ld_out, batch, KG, relu);
+    k_pn_fc_mfma<4><<<nb / 4, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, bias_ld, out, ld_out, batch, KG, relu);
   else if (cbw == 2)
-    k_pn_fc_mfma<2><<<nb / 2, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, out, ld_out, batch, KG, relu);
+    k_pn_fc_mfma<2><<<nb / 2, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, bias_ld, out, ld_out, batch, KG, relu);
   else
-    k_pn_fc_mfma<1><<<nb, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, out, ld_out, batch, KG, relu);
+    k_pn_fc_mfma<1><<<nb, kFcWaves * 64, 0, st>>>(in, ld_in, wf, bias, bias_ld, out, ld_out, batch, KG, relu);
   return hipGetLastError() == hipSuccess ? 0 : -21;
+}
+
+int ndnet_pn_fc_mfma_run(const float* in, int ld_in, const float* Wf, const float* bias, float* out, int ld_out,
+                         int batch, int K, int N, int relu, void* stream) {
+  return ndnet_pn_fc_mfma_bias_run(in, ld_in, Wf, bias, 0, out, ld_out, batch, K, N, relu, stream);
 }
 
 int ndnet_pn_cls_head_run(const float* in, int ld_in, const float* Wf, const float* bias, float* probs, int ld_probs,
@@ -2002,6 +2165,18 @@ int ndnet_pn_fold_t2_run(const float* w1f, int w1_stride, const float* b1, const
       (uintptr_t)t2 % 16)
     return -20;
   k_pn_fold_t2<<<batch, 1024, 0, (hipStream_t)stream>>>(w1f, w1_stride, b1, t2, t2_ld, outf, outb);
+  return hipGetLastError() == hipSuccess ? 0 : -21;
+}
+
+int ndnet_pn_fold_seg_run(const float* w1f, int w1_stride, const float* b1, const float* t2, int t2_ld, float* outf,
+                          float* outb, const float* s1aT, const float* s1b, int N2, float* wd, int64_t wd_stride,
+                          float* bd, int64_t bd_stride, int batch, void* stream) {
+  if (!w1f || !b1 || !t2 || !outf || !outb || !s1aT || !s1b || !wd || !bd || batch <= 0 || batch > 65535 ||
+      w1_stride < 1024 || t2_ld < 4096 || t2_ld % 4 || (uintptr_t)t2 % 16 || N2 <= 0 || N2 % 64 ||
+      (uintptr_t)s1aT % 16 || wd_stride < 16 * (int64_t)N2 || bd_stride < N2)
+    return -20;
+  k_pn_fold_seg<<<dim3(N2 / 64, batch), 1024, 0, (hipStream_t)stream>>>(w1f, w1_stride, b1, t2, t2_ld, outf, outb, s1aT,
+                                                                        s1b, N2, wd, wd_stride, bd, bd_stride);
   return hipGetLastError() == hipSuccess ? 0 : -21;
 }
 
@@ -2146,8 +2321,9 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
     int lf = 0;
     while (!args->L[lf].fuse_next) lf++;
     const int r = lf & 1, fb = fbuf_floats(qprec);
-    const int p_in = args->L[lf].prec ? 3 * kP * (args->L[lf].K + kPadB) / 2    // P's input: bf16 planes, pitch K + kPadB
-                                      : kP * ((r ? args->max_width2 : args->max_width) + kPadF);  // or fp32, region pitch
+    const int p_in = pair0_direct(*args) ? 0                                    // P reads the input rows: no tile
+                     : args->L[lf].prec ? 3 * kP * (args->L[lf].K + kPadB) / 2  // P's input: bf16 planes, pitch K + kPadB
+                                        : kP * ((r ? args->max_width2 : args->max_width) + kPadF);  // or fp32, region pitch
     const int inside = (r ? r0f : 0) + p_in;
     if (r == 1 || inside + fb <= r0f) fbuf_off = inside;
     total = fbuf_off + (size_t)fb > total ? fbuf_off + (size_t)fb : total;
@@ -2166,8 +2342,12 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
   }
   if ((args->fold_out_w || args->fold_out_b) && (!args->fold_t2 || !args->fold_out_w || !args->fold_out_b))
     PN_ARG_FAIL();
-  if (args->fold_t2) {  // the t2 fold runs in layer 0's VALU prologue, t2 staged at region 1
-    if (!valu_layer0(*args) || args->head_h2 || args->fold_ld < 4096 || args->fold_ld % 4 || (uintptr_t)args->fold_t2 % 16)
+  if (args->fold_bias && !args->fold_t2) PN_ARG_FAIL();
+  if (args->x_nonfinite_nan != 0 && args->x_nonfinite_nan != 1) PN_ARG_FAIL();
+  if (args->fold_t2) {  // the t2 fold runs in layer 0's VALU prologue (after the head prologue, if any), t2 staged at region 1
+    // fold_ld 0: one matrix for every cloud
+    if (!valu_layer0(*args) || (args->fold_ld != 0 && args->fold_ld < 4096) || args->fold_ld % 4 ||
+        (uintptr_t)args->fold_t2 % 16)
       PN_ARG_FAIL();
     if (total < (size_t)r0f + 4096) total = (size_t)r0f + 4096;
   }

@@ -179,6 +179,9 @@ POINTNET_EXPORTS: dict = {
     "ndnet_pn_cls_head_run": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, ctypes.c_int64, _P]),
     "ndnet_pn_head3_run": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ndnet_pn_fold_t2_run": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _P]),
+    "ndnet_pn_fold_seg_run": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _I,
+                                   _P]),
+    "ndnet_pn_fc_mfma_bias_run": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ndnet_pn_pool12_run": (_I, [_P, _I, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _I, _I, _P, _I,
                                  _I, _P]),
     "ndnet_pn_fold_prepare": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64)]),

@@ -16,6 +16,13 @@ with small per-cloud steps between them:
      cloud (the reference concatenates the broadcast g3 to every point:
      ndtnet.py:227-230), -> 512 -> 256 -> 128 -> C+1, log_softmax
 
+In the x6 mode chains B and D each run one layer fewer (``COLLAPSE``): nothing
+non-linear separates conv1 from TNet(64)'s first layer or from the seg head's
+conv1 on the point features, so B's layer 0 is the per-cloud 12 -> 64 layer
+relu(x (W1f[b] M) + (b1 M + bM)), composed in its prologue, and D opens with a
+per-cloud 12 -> 512 layer (``ndnet_pn_fold_seg_run`` writes its weights,
+``ndnet_pn_fc_mfma_bias_run`` its bias rows) fused into 512 -> 256.
+
 Every BatchNorm (running statistics) is folded into the preceding 1x1 conv /
 linear layer.  The per-point GEMMs run on the matrix cores: eleven layers
 (the three 128 -> 1024 / F max-pooled convs, the t2-folded conv2, the seg
@@ -123,6 +130,7 @@ MAX_FEATURE_DIM = 1024
 MAX_LAST_N = 448
 MAX_CLASSES = 1024  # NDTNetClassification: ndnet_pn_cls_head_run's padded N
 X6_LAST_MAX_N = 64  # 128 -> C+1 as a split-bf16 layer up to this padded width (_Folded)
+COLLAPSE_D_MAX_LAST_N = 256  # chain D opens with the collapsed 12 -> 512 layer up to this padded width (collapses_d)
 
 
 def supports_classification(model) -> bool:
@@ -158,7 +166,8 @@ class _Chain(ctypes.Structure):
                 ("head_w3", ctypes.c_void_p), ("head_b3", ctypes.c_void_p), ("head_basis", ctypes.c_void_p),
                 ("head_kin", ctypes.c_int32), ("head_nout", ctypes.c_int32), ("head_t1", ctypes.c_void_p),
                 ("fold_t2", ctypes.c_void_p), ("fold_ld", ctypes.c_int32), ("fold_out_w", ctypes.c_void_p),
-                ("fold_out_b", ctypes.c_void_p)]
+                ("fold_out_b", ctypes.c_void_p), ("fold_bias", ctypes.c_void_p),
+                ("x_nonfinite_nan", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
 
 
 class _FoldJob(ctypes.Structure):  # ndnet_pn_fold_job (include/ndnet_pointnet.h)
@@ -647,18 +656,62 @@ class _Workspace:
             # that chains B-D read them as layer 0's 16-byte row loads; the fourth is never used
             self.xt = torch.zeros((B, N, 4), **f32)
             self.pts = None                             # this forward's points (chain A and the transform read them)
+        # chain B collapsed (``collapses_b``), for the torch emulation: (W1 M(t1))^T M per cloud and
+        # b1^T M + bM, with (M, bM) TNet(64)'s conv1 (the HIP chain forms both in its prologue)
+        self.w1m = None if W.baseline else torch.empty((B, 12, 64), **f32)
+        self.b1m = None if W.baseline else torch.empty((64,), **f32)
         first = (W.c1T16, W.c1b) if W.baseline else (self.w1T, W.c1b)
-        self.specs = [  # torch emulation: (in_cols, [(W^T, bias)], relus, mode, kwargs)
+        layered = [  # torch emulation: (in_cols, [(W^T, bias)], relus, mode, kwargs)
             (3, W.A, (1, 1, 1), 0, dict(gmax=self.g1)),
             (kin, [first] + W.B_tail, (0, 1, 1, 1), 0, dict(gmax=self.g2)),
             (kin, [(self.w1t2, self.b1t2), W.C_mid, W.C_tail], (0, 0, 0), 0, dict(gmax=self.g3)),
         ]
         if W.seg:  # the 512-wide seg conv1 output feeds conv2 chunk by chunk (never stored whole)
-            self.specs.append((kin, [(self.w1t2, self.b1t2), (W.s1aT, self.cvec)] + W.D_tail, (0, 1, 1, 1, 0), 1,
-                               dict(out_cols=W.C1, fuse=(1,))))
+            layered.append((kin, [(self.w1t2, self.b1t2), (W.s1aT, self.cvec)] + W.D_tail, (0, 1, 1, 1, 0), 1,
+                            dict(out_cols=W.C1, fuse=(1,))))
+        collapsed = list(layered)  # conv1 and TNet(64)'s conv1 as one layer with its ReLU: three layers
+        collapsed[1] = (kin, [(self.w1m, self.b1m)] + W.B_tail[1:], (1, 1, 1), 0, dict(gmax=self.g2))
+        self._specs = {(False, False): layered, (True, False): collapsed}
+        if W.seg and not W.baseline:
+            # chain D collapsed (``collapses_d``): conv1 (t1, t2 folded) and the seg head's conv1[:, :64] as
+            # one per-cloud 12 -> 512 layer, wd[b] = w1t2[b] s1aT, with the bias cvec[b] = g3[b] s1g^T + bd[b],
+            # bd[b] = b1t2[b] s1aT + s1b (ndnet_pn_fold_seg_run; rows 12..15 of the K = 16 fragment stay zero)
+            self.wd = torch.zeros((B, 16 * 512), **f32)
+            self.bd = torch.empty((B, 512), **f32)
+            self.wdT = torch.empty((B, 12, 512), **f32)  # the same W^T plain, for the torch emulation
+            both = list(collapsed)
+            both[3] = (kin, [(self.wdT, self.cvec)] + W.D_tail, (1, 1, 1, 0), 1, dict(out_cols=W.C1, fuse=(0,)))
+            self._specs[(True, True)] = both
         self.N = N
         self.structs = {}
         self.pool12 = None  # chain C's 12 -> F argument block (``uses_pool12``), built at its first launch
+
+    def collapses_b(self, mode: str = None) -> bool:
+        """Whether chain B runs conv1 and TNet(64)'s conv1 as one per-cloud 12 -> 64 layer
+        (no ReLU separates them, ndtnet.py:149-150 and :47): ``COLLAPSE`` in the "x6" mode,
+        whose layers are fp32-accurate, with the 64 -> 64 layer it replaces a split-bf16 one
+        (``X6_NARROW``; a non-finite row then leaves both forms as zeros).  Never for the
+        baseline, whose transformed points go through a shared conv1."""
+        mode = self.mode if mode is None else mode
+        return bool(COLLAPSE) and X6_NARROW and not self.W.baseline and mode == "x6"
+
+    def collapses_d(self, mode: str = None) -> bool:
+        """Whether chain D opens with conv1 and the seg head's conv1[:, :64] as one per-cloud 12 -> 512
+        layer (no ReLU separates them either, ndtnet.py:152-157 and :227-233): where chain B collapses,
+        for a segmentation model, with ``ndnet_pn_fold_seg_run`` in ``ndnet_pn_fold_t2_run``'s place (so
+        not with NDNET_PN_FOLD_T2=chain, where chain C's prologue publishes chain D's layer 0; its bias
+        is ``ndnet_pn_fc_mfma_bias_run``'s, so not with NDNET_PN_FC=gemv).  With one layer fewer in
+        front of it, the 512 -> 256 layer's bf16 planes land in the LDS region that also holds the
+        logits, which is sized for the wider of the two: past 256 padded classes the 64-point build's
+        160 KB no longer hold it (the layered chain keeps the planes beside the logits and takes up to
+        ``MAX_LAST_N``), so such a model keeps chain D layered."""
+        return (self.collapses_b(mode) and self.W.seg and FOLD_T2_KERNEL and FC_MFMA
+                and _npad(self.W.C1) <= COLLAPSE_D_MAX_LAST_N)
+
+    @property
+    def specs(self) -> list:
+        """The chains of the current mode for the torch emulation."""
+        return self._specs[(self.collapses_b(), self.collapses_d())]
 
     def uses_pool12(self) -> bool:
         """Whether chain C runs as one ``ndnet_pn_pool12_run`` in the current mode.
@@ -687,12 +740,15 @@ class _Workspace:
         # with t1 only and t2 folded in its prologue (NDNET_PN_FOLD_T2=chain; always for the
         # baseline, whose conv1 has no per-cloud copy for ndnet_pn_fold_t2_run to read)
         LC = (self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64) if FOLD_T2_KERNEL and not W.baseline else L1
+        # chain B collapsed: layer 0 is conv1 (its prologue folds TNet(64)'s conv1 in, ``chain``)
         layers = [
             [shared(x) for x in W.A],
-            [L1] + [shared(x) for x in W.B_tail],
+            [L1] + [shared(x) for x in W.B_tail[1 if self.collapses_b(mode) else 0:]],
             [LC, shared(W.C_mid), shared(W.C_tail)],
         ]
-        if W.seg:
+        if W.seg and self.collapses_d(mode):  # 12 -> 512 per cloud on the fp32 MFMA, fused into 512 -> 256
+            layers.append([(self.wd, self.wd.stride(0), self.cvec, 16, 512)] + [shared(x) for x in W.D_tail])
+        elif W.seg:
             layers.append([(self.w1t2f, self.w1t2f.stride(0), self.b1t2, 16, 64), shared((W.s1aT, self.cvec))] +
                           [shared(x) for x in W.D_tail])
         return layers
@@ -705,13 +761,16 @@ class _Workspace:
                 kw["out"] = out
             chain_fn(x, self.N, in_cols, layers, relus, mode, **kw)
             return
-        structs = self.structs.get(self.mode)
         W = self.W
+        collapse_b, collapse_d = self.collapses_b(), self.collapses_d()
+        # argument blocks per mode and form
+        skey = self.mode if not collapse_b else (self.mode, "collapse B+D" if collapse_d else "collapse B")
+        structs = self.structs.get(skey)
         if structs is None:
             # input rows: [B,N,12] blocks; the baseline's chain A reads the points themselves, B-D ws.xt
             x_lds = (3, 4, 4, 4) if W.baseline else (12, 12, 12, 12)
-            structs = self.structs[self.mode] = [_build_chain(self.N, s[0], hl, s[2], s[3], x_ld=xl, **s[4])
-                                                 for s, hl, xl in zip(self.specs, self.hip_layers(self.mode), x_lds)]
+            structs = self.structs[skey] = [_build_chain(self.N, s[0], hl, s[2], s[3], x_ld=xl, **s[4])
+                                            for s, hl, xl in zip(self.specs, self.hip_layers(self.mode), x_lds)]
             if W.seg:  # the last chain re-arms the max-pool buffer (-inf) for the next forward
                 structs[3].clear = self.gbuf.data_ptr()
                 structs[3].clear_count = self.gbuf.numel()
@@ -721,6 +780,17 @@ class _Workspace:
                 cb.head_w3, cb.head_b3 = W.t1["f3"].data_ptr(), W.t1["c3"].data_ptr()
                 cb.head_basis, cb.head_kin, cb.head_nout = W.t1_basis.data_ptr(), 12, 64
                 cb.head_t1 = self.t1.data_ptr()
+            if collapse_b:
+                # chain B: TNet(64)'s conv1 (M, bM: shared, hot) folded through conv1 in the prologue,
+                # after the head prologue -- layer 0 = relu(x (W1f[b] M) + (b1 M + bM)).  Formed from
+                # the live folded tensors at every launch: an in-place re-fold is followed
+                cb = structs[1]
+                m_w, m_b = W.B_tail[0]
+                assert m_w.shape == (64, 64) and m_w.is_contiguous() and m_b.shape == (64,)
+                cb.fold_t2, cb.fold_ld, cb.fold_bias = m_w.data_ptr(), 0, m_b.data_ptr()
+                cb.x_nonfinite_nan = 1  # a NaN / inf row leaves the first ReLU as zeros, as the layered pair's
+            if collapse_d:
+                structs[3].x_nonfinite_nan = 1
             if not FOLD_T2_KERNEL or W.baseline:  # chain C: t2 through layer 0 (prologue fold), published for chain D
                 cc = structs[2]
                 cc.fold_t2, cc.fold_ld = self.t2.data_ptr(), self.t2.stride(0)
@@ -775,6 +845,14 @@ FOLD_T2_KERNEL = os.environ.get("NDNET_PN_FOLD_T2", "kernel") == "kernel"
 BACKBONE = os.environ.get("NDNET_PN_BACKBONE", "pool12")
 if BACKBONE not in ("pool12", "chain"):
     raise ValueError(f"NDNET_PN_BACKBONE must be 'pool12' or 'chain', not {BACKBONE!r}")
+# Chain B's first two layers, conv1 (t1 folded) and TNet(64)'s conv1, have no ReLU between them
+# (ndtnet.py:149-150, :47): "1" (default) runs them as one per-cloud 12 -> 64 VALU layer whose
+# weights chain B's prologue composes (ndnet_pn_chain.fold_t2 with a shared matrix and fold_bias),
+# wherever ``_Workspace.collapses_b`` allows; and chain D's conv1 (t1, t2 folded) and the seg head's
+# conv1[:, :64] as one per-cloud 12 -> 512 layer on the fp32 MFMA (``_Workspace.collapses_d``).
+# "0" keeps the layered launches, bit for bit.  A module attribute read when a forward picks its
+# argument blocks, like BACKBONE.
+COLLAPSE = os.environ.get("NDNET_PN_COLLAPSE", "1") == "1"
 # TNet(3)'s tail (fc3 + the t1 fold of conv1): "chain" (default) computes it in
 # chain B's prologue, per workgroup (ndnet_pn_chain.head_*: one launch and one
 # boundary fewer); "kernel" runs ndnet_pn_head3_run before chain B
@@ -847,14 +925,31 @@ def _glue_hip(W, ws, B: int):
         fc(ws.g2, t["f1"], t["c1"], ws.h1, True)
         fc(ws.h1, t["f2"], t["c2"], ws.h2, True)
         fc(ws.h2, t["f3"], t["c3"], ws.t2, False)  # t2
-        if FOLD_T2_KERNEL and not W.baseline:  # t2 through conv1: chains C / D's layer 0, once per cloud
+        if ws.collapses_d():  # the same, and the seg head's conv1 through it: chain D's first layer (wd, bd)
+            assert W.s1aT.shape == (64, 512) and W.s1aT.is_contiguous()
+            rc = _lib.lib().ndnet_pn_fold_seg_run(ws.w1f.data_ptr(), ws.w1f.stride(0), W.c1b.data_ptr(),
+                                                  ws.t2.data_ptr(), ws.t2.stride(0), ws.w1t2f.data_ptr(),
+                                                  ws.b1t2.data_ptr(), W.s1aT.data_ptr(), W.s1b.data_ptr(), 512,
+                                                  ws.wd.data_ptr(), ws.wd.stride(0), ws.bd.data_ptr(),
+                                                  ws.bd.stride(0), B, st())
+            _lib.check(rc, "ndnet_pn_fold_seg_run")
+        elif FOLD_T2_KERNEL and not W.baseline:  # t2 through conv1: chains C / D's layer 0, once per cloud
             rc = _lib.lib().ndnet_pn_fold_t2_run(ws.w1f.data_ptr(), ws.w1f.stride(0), W.c1b.data_ptr(),
                                                  ws.t2.data_ptr(), ws.t2.stride(0), ws.w1t2f.data_ptr(),
                                                  ws.b1t2.data_ptr(), B, st())
             _lib.check(rc, "ndnet_pn_fold_t2_run")
 
     def seg_bias():
-        fc(ws.g3[:, : W.F], W.s1g, W.s1b, ws.cvec, False)
+        if not ws.collapses_d():
+            fc(ws.g3[:, : W.F], W.s1g, W.s1b, ws.cvec, False)
+            return
+        # chain D collapsed: the bias row of each cloud is bd[b] (which holds s1b), ndnet_pn_fold_seg_run's
+        wf = W.fcf[id(W.s1g)]
+        for c0 in range(0, B, 16):
+            rc = _lib.lib().ndnet_pn_fc_mfma_bias_run(ws.g3[c0].data_ptr(), ws.g3.stride(0), wf.data_ptr(),
+                                                      ws.bd[c0].data_ptr(), ws.bd.stride(0), ws.cvec[c0].data_ptr(),
+                                                      ws.cvec.stride(0), min(16, B - c0), _pad(W.F, 16), 512, 0, st())
+            _lib.check(rc, "ndnet_pn_fc_mfma_bias_run")
 
     def cls_head(out):
         # g3's columns past F are chain C's zero padding, matched by zero weight rows
@@ -873,6 +968,10 @@ def _glue_torch(W, ws, B: int):
     def head_a():
         t1 = _fc_head(ws.g1, W.t1, 3, ws.h1, ws.h2, ws.t1)
         torch.matmul(t1.reshape(B, 9), W.t1_basis, out=ws.w1T.view(B, 12 * 64))
+        if ws.collapses_b():  # chain B's composed layer 0 (the HIP chain's prologue)
+            m_w, m_b = W.B_tail[0]
+            torch.matmul(ws.w1T, m_w, out=ws.w1m)
+            torch.addmv(m_b, m_w.t(), W.c1b, out=ws.b1m)
 
     def head_a_points():
         t1 = _fc_head(ws.g1, W.t1, 3, ws.h1, ws.h2, ws.t1)
@@ -882,9 +981,12 @@ def _glue_torch(W, ws, B: int):
         t2 = _fc_head(ws.g2, W.t2, 64, ws.h1, ws.h2, ws.t2)
         torch.matmul(W.c1wT if W.baseline else ws.w1T, t2, out=ws.w1t2)
         torch.matmul(W.c1b[None, None, :], t2, out=ws.b1t2.view(B, 1, 64))
+        if ws.collapses_d():  # chain D's composed first layer (ndnet_pn_fold_seg_run)
+            torch.matmul(ws.w1t2, W.s1aT, out=ws.wdT)
+            torch.addmm(W.s1b, ws.b1t2, W.s1aT, out=ws.bd)
 
     def seg_bias():
-        torch.addmm(W.s1b, ws.g3[:, : W.F], W.s1bT, out=ws.cvec)
+        torch.addmm(ws.bd if ws.collapses_d() else W.s1b, ws.g3[:, : W.F], W.s1bT, out=ws.cvec)
 
     def cls_head(out):
         torch.addmm(W.h1b, ws.g3[:, : W.F], W.h1w[:, :, 0].t(), out=ws.h1).relu_()
