@@ -232,22 +232,40 @@ int ndnet_pn_cls_head_run(const float *in, int ld_in, const float *Wf, const flo
  *   NDNET_FOLD_BIAS   out[n] (Np floats) = (bias[n] - mean[n]) * s[n] + beta[n]
  *                     (no BatchNorm: bias[n]), + 1 on the diagonal of an
  *                     eye x eye matrix when eye > 0, zero padded
+ *   NDNET_FOLD_PROD   a product of two tensors that other jobs of the list write
+ *                     (or of any fp32 tensors), for the forward's weight-only products:
+ *                       out[r][n] = sum_k w[r * ld + k0 + k] * rhs[k * Np + n]  (+ bias[n]),
+ *                     r < N, k < K, n < Np; `w` is the left factor as it is (no BatchNorm:
+ *                     gamma must be NULL), rhs the right one, K x Np row-major, bias an
+ *                     optional row added to every output row.  Each fp32 x fp32 product is
+ *                     exact in double; the sum runs in double with k ascending (bias last)
+ *                     and is rounded once at the store.  out_f64 = 1 stores the doubles
+ *                     themselves: `out` is then N x Np DOUBLES -- the one output type of
+ *                     the table that is neither fp32 nor bf16 (ndnet_pn_pool12_tail_run's
+ *                     w23 and b23) -- else N x Np floats.
+ *                     PROD jobs read what the other kinds write, so they must be the
+ *                     list's last jobs; ndnet_pn_fold_run runs them as a second launch
+ *                     behind the first, in stream order.
  * ndnet_pn_fold_prepare validates a host copy of the job list and fills each
  * job's block0 (its first workgroup), returning the grid size in
- * *num_blocks; ndnet_pn_fold_run then runs the list from DEVICE memory in
- * one launch (graph-capturable, no allocation).  NDNET_ERR_ARG (-20) on an
- * invalid job. */
+ * *num_blocks (the list's workgroups in the lower 32 bits, those of its PROD
+ * jobs in the upper: pass it on as it is); ndnet_pn_fold_run then runs the
+ * list from DEVICE memory in one launch, two with PROD jobs
+ * (graph-capturable, no allocation).  NDNET_ERR_ARG (-20) on an invalid job
+ * or a PROD job followed by one of another kind. */
 #define NDNET_FOLD_WT 0
 #define NDNET_FOLD_FRAG 1
 #define NDNET_FOLD_FRAG6 2
 #define NDNET_FOLD_ROWS 3
 #define NDNET_FOLD_BASIS 4
 #define NDNET_FOLD_BIAS 5
+#define NDNET_FOLD_PROD 6
 typedef struct ndnet_pn_fold_job {
   const float *w;                          /* layer weight, rows of ld floats (not read by BIAS) */
   const float *bias;                       /* layer bias [N] (BIAS only) */
   const float *gamma, *beta, *mean, *var;  /* BatchNorm1d weight, bias, running mean / var; NULL: none */
-  void *out;                               /* the output tensor (bf16 for FRAG6, else fp32), 16-byte aligned */
+  void *out;                               /* the output tensor (bf16 for FRAG6, double for PROD with out_f64,
+                                              else fp32), 16-byte aligned */
   int32_t kind;
   int32_t N, K;                            /* layer rows (outputs) and the input columns used */
   int32_t ld, k0;                          /* row stride of w and the first column used */
@@ -256,6 +274,10 @@ typedef struct ndnet_pn_fold_job {
   float eps;
   int32_t reserved;
   int64_t block0;                          /* filled by ndnet_pn_fold_prepare */
+  /* Fields added after the first release of this struct (PROD only; zero otherwise). */
+  const float *rhs;                        /* the right factor, K x Np floats row-major */
+  int32_t out_f64;                         /* 1: `out` is N x Np doubles; 0: floats */
+  int32_t reserved1;
 } ndnet_pn_fold_job;
 int ndnet_pn_fold_prepare(ndnet_pn_fold_job *host_jobs, int num_jobs, int64_t *num_blocks);
 int ndnet_pn_fold_run(const ndnet_pn_fold_job *device_jobs, int num_jobs, int64_t num_blocks, void *stream);
@@ -330,6 +352,23 @@ int ndnet_pn_pool12_run(const float *x, int x_ld, int num_points, const float *w
                         const float *b0, int64_t b0_stride, const float *w_mid, const float *b_mid,
                         const float *w_tail, const float *b_tail, int F, int Fp, float *gmax, int gmax_ld,
                         int batch, void *stream);
+
+/* The same launch from the composed tail: w_mid w_tail and its bias row do not
+ * depend on the cloud, so the fold forms them once (two NDNET_FOLD_PROD jobs
+ * with out_f64 = 1, re-run by every in-place re-fold) and each workgroup's
+ * slice is the one product
+ *   [Wc[b]; bc[b]] = [W0[b]; b0[b]] w23  (+ b23 on the bias row),
+ *   w23 = w_mid w_tail (64 x Fp doubles, row-major),  b23 = b_mid w_tail + b_tail (Fp doubles),
+ * on the f64 MFMA, rounded once to fp32 -- a quarter of ndnet_pn_pool12_run's
+ * matrix work per workgroup and no intermediate.  The value differs from that
+ * entry's only in the order of the double sums (W0 (w_mid w_tail) for
+ * (W0 w_mid) w_tail).  Everything after it -- the rows, the NaN and infinity
+ * rule, the maximum, the store, the grid -- is ndnet_pn_pool12_run's, and so
+ * are the other arguments and the return codes; w23 and b23 must be 8-byte
+ * aligned.  Nothing is cached: w23 and b23 are read at every launch. */
+int ndnet_pn_pool12_tail_run(const float *x, int x_ld, int num_points, const float *w0f, int64_t w0_stride,
+                             const float *b0, int64_t b0_stride, const double *w23, const double *b23, int Fp,
+                             float *gmax, int gmax_ld, int batch, void *stream);
 
 #ifdef __cplusplus
 }

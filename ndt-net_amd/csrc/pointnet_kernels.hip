@@ -1763,12 +1763,18 @@ __device__ inline void p12_clean(int n, int tile, int cl, float (&v)[3]) {
   for (int s = 0; s < 3; s++) v[s] = (in & (fabsf(v[s]) < INFINITY)) ? v[s] : NAN;  // & : one select, no branch
 }
 
+// kTail: phase 1 from the composed tail (ndnet_pn_pool12_tail_run) -- w23 = W2'^T W3'^T (64 x Fp doubles) and
+// its bias row b23 = b2' W3'^T + b3', both outputs of the fold's job table, so the slice is the one product
+// [W0''; b0''] (13 x 64) w23[:, c0 .. c0 + 64): waves 0..3, one on each SIMD, 16 columns and 16 MFMAs each on
+// four independent accumulators.  That is a quarter of the layered product's MFMAs per SIMD, and neither the
+// 13 x 128 intermediate nor its barrier.  w_mid, b_mid, w_tail, b_tail are then not read.
+template <bool kTail>
 __global__ void __launch_bounds__(kP12Waves * 64) k_pn_pool12(
     const float* __restrict__ x, int x_ld, int n, const float* __restrict__ w0f, int64_t w0_stride,
     const float* __restrict__ b0, int64_t b0_stride, const float* __restrict__ w_mid,
-    const float* __restrict__ b_mid, const float* __restrict__ w_tail, const float* __restrict__ b_tail, int Fp,
-    float* __restrict__ gmax, int gmax_ld) {
-  __shared__ double s_m[13 * kP12Pitch];     // [W0''; b0''] W2'^T (+ b2' on row 12)
+    const float* __restrict__ b_mid, const float* __restrict__ w_tail, const float* __restrict__ b_tail,
+    const double* __restrict__ w23, const double* __restrict__ b23, int Fp, float* __restrict__ gmax, int gmax_ld) {
+  __shared__ double s_m[kTail ? 1 : 13 * kP12Pitch];  // [W0''; b0''] W2'^T (+ b2' on row 12)
   __shared__ float s_wc[13 * 64];            // this workgroup's columns of [Wc; bc]
   __shared__ float s_red[kP12Waves * 64];
   const int b = blockIdx.y, c0 = 64 * blockIdx.x;
@@ -1783,6 +1789,40 @@ __global__ void __launch_bounds__(kP12Waves * 64) k_pn_pool12(
   for (int i = 0; i < kP12Pre; i++) p12_rows(xb, x_ld, n, wave + kP12Waves * i, kq, cl, xp[i]);
   float tw[32];  // waves 8..11 (phase 1b): W3'^T[4 ks + kq][c0 + 16 (wave - 8) + cl]
 
+  if constexpr (kTail) {
+    // phase 1, waves 0..3: A = [W0''; b0''] (row cl of 16, 13 used) as phase 1a reads it, B = w23's column
+    // c0 + 16 wave + cl; v_mfma_f64_16x16x4_f64 leaves row kq + 4 q, column cl in element q
+    if (wave < 4) {
+      const float* wb = w0f + (int64_t)b * w0_stride;
+      const float* bb = b0 + (int64_t)b * b0_stride;
+      const int tc = min(c0 + 16 * wave + cl, Fp - 1);  // Fp = 32: the upper half's columns are never stored
+      float a[16];
+      double bw[16];
+#pragma unroll
+      for (int ks = 0; ks < 16; ks++) {
+        const int i = 4 * ks + kq;
+        const float* src = cl < 12 ? wb + ((((i >> 4) * 64 + ((cl >> 2) & 3) * 16 + (i & 15)) << 2) + (cl & 3)) : bb + i;
+        a[ks] = *src;  // rows 13..15 read the bias too and are zeroed below: one load, no branch
+        bw[ks] = w23[(int64_t)i * Fp + tc];
+      }
+      const double brow = b23[tc];
+#pragma unroll
+      for (int ks = 0; ks < 16; ks++) a[ks] = cl < 13 ? a[ks] : 0.0f;
+      f64x4 acc[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) acc[j] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int ks = 0; ks < 16; ks++)
+        acc[ks & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)a[ks], bw[ks], acc[ks & 3], 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int row = kq + 4 * q, col = 16 * wave + cl;
+        double v = (acc[0][q] + acc[1][q]) + (acc[2][q] + acc[3][q]);
+        if (row == 12) v += brow;
+        if (row < 13) s_wc[row * 64 + col] = (float)v;
+      }
+    }
+  } else {
   // phase 1a, waves 0..7, 16 columns of the intermediate each: A = [W0''; b0''] (row cl of 16, 13 used),
   // B = W2'^T; v_mfma_f64_16x16x4_f64 leaves row kq + 4 q, column cl in element q
   if (wave < 8) {
@@ -1835,6 +1875,7 @@ __global__ void __launch_bounds__(kP12Waves * 64) k_pn_pool12(
       if (row < 13) s_wc[row * 64 + col] = (float)v;
     }
   }
+  }  // !kTail
   __syncthreads();
 
   // phase 2: A = the slice (lane (kq, cl): row 4 s + kq, column 16 cb + cl), B = the tile's rows;
@@ -1996,17 +2037,22 @@ __host__ __device__ inline int64_t fold_units(const ndnet_pn_fold_job& J) {
     case NDNET_FOLD_FRAG6: return (int64_t)J.Kp * J.Np / 8;
     case NDNET_FOLD_ROWS: return (int64_t)J.N * J.K;
     case NDNET_FOLD_BASIS: return (int64_t)9 * J.K * J.N;
+    case NDNET_FOLD_PROD: return (int64_t)J.N * J.Np;
     default: return J.Np;
   }
 }
 
-__global__ void __launch_bounds__(kFoldThreads) k_pn_fold(const ndnet_pn_fold_job* __restrict__ jobs, int num_jobs) {
+// block_base: the launch's first block of the list.  The product jobs read other jobs' outputs, so they are
+// the list's last blocks and run as a second launch behind the first (ndnet_pn_fold_run).
+__global__ void __launch_bounds__(kFoldThreads) k_pn_fold(const ndnet_pn_fold_job* __restrict__ jobs, int num_jobs,
+                                                          int64_t block_base) {
 #pragma clang fp contract(off)
+  const int64_t blk = block_base + blockIdx.x;
   int j = 0;  // this workgroup's job: the last one starting at or before it (block0 ascends)
   for (int i = 1; i < num_jobs; i++)
-    if (jobs[i].block0 <= (int64_t)blockIdx.x) j = i;
+    if (jobs[i].block0 <= blk) j = i;
   const ndnet_pn_fold_job J = jobs[j];
-  const int64_t u = ((int64_t)blockIdx.x - J.block0) * kFoldThreads + threadIdx.x;
+  const int64_t u = (blk - J.block0) * kFoldThreads + threadIdx.x;
   if (u >= fold_units(J)) return;
   switch (J.kind) {
     case NDNET_FOLD_WT: {
@@ -2063,6 +2109,16 @@ __global__ void __launch_bounds__(kFoldThreads) k_pn_fold(const ndnet_pn_fold_jo
         v = fold_w(J, n, 3 + 3 * a + (r - 3) % 3);
       }
       static_cast<float*>(J.out)[u] = v;
+      break;
+    }
+    case NDNET_FOLD_PROD: {  // out[r][n] = sum_k w[r][k] rhs[k][n] (+ bias[n]): double, k ascending, rounded at the store
+      const int n = (int)(u % J.Np), r = (int)(u / J.Np);
+      const float* a = J.w + (int64_t)r * J.ld + J.k0;
+      double acc = 0.0;
+      for (int k = 0; k < J.K; k++) acc += (double)a[k] * (double)J.rhs[(int64_t)k * J.Np + n];  // the product is exact
+      if (J.bias) acc += (double)J.bias[n];
+      if (J.out_f64) static_cast<double*>(J.out)[u] = acc;
+      else static_cast<float*>(J.out)[u] = (float)acc;
       break;
     }
     default: {  // NDNET_FOLD_BIAS
@@ -2187,18 +2243,38 @@ int ndnet_pn_pool12_run(const float* x, int x_ld, int num_points, const float* w
       num_points <= 0 || x_ld < 12 || x_ld % 4 || w0_stride < 1024 || b0_stride < 64 || F <= 0 || F > Fp ||
       (Fp != 32 && Fp % 64) || gmax_ld < Fp)
     return -20;
-  k_pn_pool12<<<dim3((Fp + 63) / 64, batch), kP12Waves * 64, 0, (hipStream_t)stream>>>(
-      x, x_ld, num_points, w0f, w0_stride, b0, b0_stride, w_mid, b_mid, w_tail, b_tail, Fp, gmax, gmax_ld);
+  k_pn_pool12<false><<<dim3((Fp + 63) / 64, batch), kP12Waves * 64, 0, (hipStream_t)stream>>>(
+      x, x_ld, num_points, w0f, w0_stride, b0, b0_stride, w_mid, b_mid, w_tail, b_tail, nullptr, nullptr, Fp, gmax,
+      gmax_ld);
+  return hipGetLastError() == hipSuccess ? 0 : -21;
+}
+
+int ndnet_pn_pool12_tail_run(const float* x, int x_ld, int num_points, const float* w0f, int64_t w0_stride,
+                             const float* b0, int64_t b0_stride, const double* w23, const double* b23, int Fp,
+                             float* gmax, int gmax_ld, int batch, void* stream) {
+  if (!x || !w0f || !b0 || !w23 || !b23 || !gmax || batch <= 0 || batch > 65535 || num_points <= 0 || x_ld < 12 ||
+      x_ld % 4 || w0_stride < 1024 || b0_stride < 64 || Fp <= 0 || (Fp != 32 && Fp % 64) || gmax_ld < Fp ||
+      ((uintptr_t)w23 | (uintptr_t)b23) % 8)
+    return -20;
+  k_pn_pool12<true><<<dim3((Fp + 63) / 64, batch), kP12Waves * 64, 0, (hipStream_t)stream>>>(
+      x, x_ld, num_points, w0f, w0_stride, b0, b0_stride, nullptr, nullptr, nullptr, nullptr, w23, b23, Fp, gmax,
+      gmax_ld);
   return hipGetLastError() == hipSuccess ? 0 : -21;
 }
 
 int ndnet_pn_fold_prepare(ndnet_pn_fold_job* jobs, int num_jobs, int64_t* num_blocks) {
   if (!jobs || num_jobs <= 0 || !num_blocks) return -20;
-  int64_t blocks = 0;
+  int64_t blocks = 0, prod0 = -1;  // prod0: the first block of the product jobs, which close the list
   for (int i = 0; i < num_jobs; i++) {
     ndnet_pn_fold_job& J = jobs[i];
     const bool bn = J.gamma != nullptr;
-    if (!J.out || (uintptr_t)J.out % 16 || J.kind < NDNET_FOLD_WT || J.kind > NDNET_FOLD_BIAS || J.N <= 0 ||
+    if (J.kind == NDNET_FOLD_PROD) {
+      if (bn || !J.rhs || J.Np <= 0 || (J.out_f64 != 0 && J.out_f64 != 1)) return -20;
+      if (prod0 < 0) prod0 = blocks;
+    } else if (prod0 >= 0) {
+      return -20;
+    }
+    if (!J.out || (uintptr_t)J.out % 16 || J.kind < NDNET_FOLD_WT || J.kind > NDNET_FOLD_PROD || J.N <= 0 ||
         (bn && (!J.beta || !J.mean || !J.var || !(J.eps >= 0.0f))) || (!bn && (J.beta || J.mean || J.var)))
       return -20;
     if (J.kind == NDNET_FOLD_BIAS) {
@@ -2214,13 +2290,16 @@ int ndnet_pn_fold_prepare(ndnet_pn_fold_job* jobs, int num_jobs, int64_t* num_bl
     blocks += (fold_units(J) + kFoldThreads - 1) / kFoldThreads;
   }
   if (blocks <= 0 || blocks > 0x7fffffff) return -20;
-  *num_blocks = blocks;
+  *num_blocks = blocks | ((prod0 < 0 ? 0 : blocks - prod0) << 32);  // the product jobs' blocks in the upper half
   return 0;
 }
 
 int ndnet_pn_fold_run(const ndnet_pn_fold_job* jobs, int num_jobs, int64_t num_blocks, void* stream) {
-  if (!jobs || num_jobs <= 0 || num_blocks <= 0 || num_blocks > 0x7fffffff) return -20;
-  k_pn_fold<<<(unsigned)num_blocks, kFoldThreads, 0, (hipStream_t)stream>>>(jobs, num_jobs);
+  const int64_t blocks = num_blocks & 0xffffffff, prod = num_blocks >> 32;
+  if (!jobs || num_jobs <= 0 || blocks <= 0 || blocks > 0x7fffffff || prod < 0 || prod > blocks) return -20;
+  if (blocks > prod) k_pn_fold<<<(unsigned)(blocks - prod), kFoldThreads, 0, (hipStream_t)stream>>>(jobs, num_jobs, 0);
+  // the products of what the first launch has just written, behind it in stream order
+  if (prod) k_pn_fold<<<(unsigned)prod, kFoldThreads, 0, (hipStream_t)stream>>>(jobs, num_jobs, blocks - prod);
   return hipGetLastError() == hipSuccess ? 0 : -21;
 }
 

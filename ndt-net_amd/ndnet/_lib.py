@@ -184,6 +184,7 @@ POINTNET_EXPORTS: dict = {
     "ndnet_pn_fc_mfma_bias_run": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ndnet_pn_pool12_run": (_I, [_P, _I, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _I, _I, _P, _I,
                                  _I, _P]),
+    "ndnet_pn_pool12_tail_run": (_I, [_P, _I, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _I, _P, _I, _I, _P]),
     "ndnet_pn_fold_prepare": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64)]),
     "ndnet_pn_fold_run": (_I, [_P, _I, ctypes.c_int64, _P]),
 }

@@ -11,7 +11,9 @@ with small per-cloud steps between them:
      FC head (1024 -> 512 -> 256 -> 4096) + I                    -> t2
   C  conv2 with t2^T folded in (x_t2 = t2^T x1), conv3, max      -> g3 [F]
      (no ReLU in it: in the x6 / fp32 modes one per-cloud 12 -> F layer,
-     ``ndnet_pn_pool12_run``, in the chain's place; ``BACKBONE``)
+     ``ndnet_pn_pool12_run``, in the chain's place; ``BACKBONE``; by default
+     from the fold's composed tail W2'^T W3'^T, ``ndnet_pn_pool12_tail_run``;
+     ``FOLD_PRODUCTS``)
   D  seg conv1 split: W[:, :64] t2^T x1 per point + (W[:, 64:] g3 + b) per
      cloud (the reference concatenates the broadcast g3 to every point:
      ndtnet.py:227-230), -> 512 -> 256 -> 128 -> C+1, log_softmax
@@ -176,7 +178,8 @@ class _FoldJob(ctypes.Structure):  # ndnet_pn_fold_job (include/ndnet_pointnet.h
                 ("out", ctypes.c_void_p), ("kind", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
                 ("ld", ctypes.c_int32), ("k0", ctypes.c_int32), ("Kp", ctypes.c_int32), ("Np", ctypes.c_int32),
                 ("eye", ctypes.c_int32), ("eps", ctypes.c_float), ("reserved", ctypes.c_int32),
-                ("block0", ctypes.c_int64)]
+                ("block0", ctypes.c_int64), ("rhs", ctypes.c_void_p), ("out_f64", ctypes.c_int32),
+                ("reserved1", ctypes.c_int32)]
 
 
 
@@ -237,6 +240,16 @@ def _frag_x6(wT: torch.Tensor) -> torch.Tensor:
     return v.permute(4, 1, 0, 2, 5, 3).reshape(-1).contiguous()        # cb, kg, plane, kq, cl, j
 
 
+def _prod64(a: torch.Tensor, rhs: torch.Tensor, bias=None) -> torch.Tensor:
+    """a @ rhs (+ bias on every row) as an NDNET_FOLD_PROD job forms it, bit for bit: fp32 factors, each
+    product exact in float64, the sum in float64 with k ascending, the bias last."""
+    a, rhs = a.reshape(-1, a.shape[-1]).double(), rhs.double()
+    acc = torch.zeros((a.shape[0], rhs.shape[1]), dtype=torch.float64, device=a.device)
+    for k in range(a.shape[1]):
+        acc += a[:, k, None] * rhs[k]
+    return acc if bias is None else acc + bias.double()
+
+
 def _bpad(b: torch.Tensor, npad: int) -> torch.Tensor:
     out = torch.zeros(npad, dtype=torch.float32, device=b.device)
     out[: b.shape[0]] = b
@@ -281,10 +294,20 @@ class _Folded:
                            (_wT(t2["w3"], 128, 1024), t2["b3"])]
             self.C_tail = (_wT(self.c3w, 128, _npad(F)), _bpad(self.c3b, _npad(F)))
             self.c1wT = self.c1w.t().contiguous()         # [12, 64]
+            # weight-only products of the forward (``FOLD_PRODUCTS``), each (out, left, right, bias row or
+            # None) an NDNET_FOLD_PROD job behind ``jobs`` in the device table, so a re-fold recomputes it
+            self.products = []
             # x_t2 = t2^T x1 (ndtnet.py:152-157) feeds conv2 and the seg head's
             # conv1a; t2 is folded into chains C / D's layer 0 (their prologue,
             # ndnet_pn_chain.fold_t2), so both layers keep shared weights
             self.C_mid = (_wT(self.c2w, 64, 128), self.c2b)          # conv2 W^T [64, 128]
+            if not self.baseline:
+                # chain C's composed tail for ndnet_pn_pool12_tail_run, kept in float64:
+                # W23 = W2'^T W3'^T (64 x Fp), b23 = b2' W3'^T + b3' (Fp)
+                self.W23 = _prod64(self.C_mid[0], self.C_tail[0])
+                self.b23 = _prod64(self.c2b[None, :], self.C_tail[0], self.C_tail[1]).reshape(-1)
+                self.products += [(self.W23, self.C_mid[0], self.C_tail[0], None),
+                                  (self.b23, self.c2b, self.C_tail[0], self.C_tail[1])]
             # conv1 of the t1-transformed input: (W1 M(t1))^T = sum_ac t1[a,c] E_ac^T W1^T,
             # M(t1) = blockdiag(t1, kron(t1, I3)) (p' = t1 p, C' = t1 C)
             dev = self.c1wT.device
@@ -474,7 +497,16 @@ class _Folded:
         that point at these tensors stay valid)."""
         dev = self.c1wT.device
         if self._dev_jobs is None:
-            arr = (_FoldJob * len(self.jobs))()
+            arr = (_FoldJob * (len(self.jobs) + len(self.products)))()
+            for i, (out, a, rhs, bias) in enumerate(self.products, len(self.jobs)):
+                J = arr[i]
+                assert a.is_contiguous() and rhs.is_contiguous() and rhs.dim() == 2 and out.is_contiguous()
+                J.kind, J.out, J.w, J.rhs = 6, out.data_ptr(), a.data_ptr(), rhs.data_ptr()
+                J.K, J.ld, J.Np = rhs.shape[0], rhs.shape[0], rhs.shape[1]
+                J.N = a.numel() // J.K
+                J.bias = bias.data_ptr() if bias is not None else None
+                J.out_f64 = 1 if out.dtype == torch.float64 else 0
+                assert out.numel() == J.N * J.Np
             for J, (kind, out, layer, bn, k0, K, Kp, Np, eye) in zip(arr, self.jobs):
                 J.kind, J.out, J.N, J.K, J.ld, J.k0 = kind, out.data_ptr(), layer.weight.shape[0], K, \
                     layer.weight.shape[1], k0
@@ -490,8 +522,8 @@ class _Folded:
             _lib.check(_lib.lib().ndnet_pn_fold_prepare(arr, len(arr), ctypes.byref(blocks)), "ndnet_pn_fold_prepare")
             self._dev_jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
             self._blocks = blocks.value
-        rc = _lib.lib().ndnet_pn_fold_run(self._dev_jobs.data_ptr(), len(self.jobs), self._blocks,
-                                          _lib.stream_ptr(dev))
+        rc = _lib.lib().ndnet_pn_fold_run(self._dev_jobs.data_ptr(), len(self.jobs) + len(self.products),
+                                          self._blocks, _lib.stream_ptr(dev))
         _lib.check(rc, "ndnet_pn_fold_run")
 
 
@@ -571,22 +603,29 @@ class _Pool12:
     reads their addresses once, as ``_build_chain`` does; the kernel reads
     their contents at every launch, so an in-place re-fold is followed."""
 
-    def __init__(self, ws: "_Workspace") -> None:
+    def __init__(self, ws: "_Workspace", tail: bool = False) -> None:
         W = ws.W
         (w_mid, b_mid), (w_tail, b_tail) = W.C_mid, W.C_tail
         assert w_mid.shape == (64, 128) and w_mid.is_contiguous() and w_tail.shape[0] == 128 and w_tail.is_contiguous()
-        self.tensors = (ws.w1t2f, ws.b1t2, w_mid, b_mid, w_tail, b_tail, ws.g3)
         self.n, self.F, self.Fp = ws.N, W.F, w_tail.shape[1]
-        self.args = (ws.w1t2f.data_ptr(), ws.w1t2f.stride(0), ws.b1t2.data_ptr(), ws.b1t2.stride(0),
-                     w_mid.data_ptr(), b_mid.data_ptr(), w_tail.data_ptr(), b_tail.data_ptr(), self.F, self.Fp,
-                     ws.g3.data_ptr(), ws.g3.stride(0))
+        self.tail = tail  # ``ndnet_pn_pool12_tail_run`` on the fold's W23, b23 (``FOLD_PRODUCTS``)
+        head = (ws.w1t2f.data_ptr(), ws.w1t2f.stride(0), ws.b1t2.data_ptr(), ws.b1t2.stride(0))
+        if tail:
+            assert W.W23.shape == (64, self.Fp) and W.W23.dtype == W.b23.dtype == torch.float64
+            self.tensors = (ws.w1t2f, ws.b1t2, W.W23, W.b23, ws.g3)
+            self.args = head + (W.W23.data_ptr(), W.b23.data_ptr(), self.Fp, ws.g3.data_ptr(), ws.g3.stride(0))
+            return
+        self.tensors = (ws.w1t2f, ws.b1t2, w_mid, b_mid, w_tail, b_tail, ws.g3)
+        self.args = head + (w_mid.data_ptr(), b_mid.data_ptr(), w_tail.data_ptr(), b_tail.data_ptr(), self.F, self.Fp,
+                            ws.g3.data_ptr(), ws.g3.stride(0))
 
 
 def _run_pool12(blk: "_Pool12", x: torch.Tensor) -> None:
     B, n, _ = x.shape
     assert n == blk.n and x.stride(2) == 1 and x.stride(0) == n * x.stride(1) and x.dtype == torch.float32
-    rc = _lib.lib().ndnet_pn_pool12_run(x.data_ptr(), x.stride(1), n, *blk.args, B, _lib.stream_ptr(x.device))
-    _lib.check(rc, "ndnet_pn_pool12_run")
+    name = "ndnet_pn_pool12_tail_run" if blk.tail else "ndnet_pn_pool12_run"
+    rc = getattr(_lib.lib(), name)(x.data_ptr(), x.stride(1), n, *blk.args, B, _lib.stream_ptr(x.device))
+    _lib.check(rc, name)
 
 
 def _run_chain(ch, x: torch.Tensor, out=None) -> None:
@@ -685,6 +724,7 @@ class _Workspace:
         self.N = N
         self.structs = {}
         self.pool12 = None  # chain C's 12 -> F argument block (``uses_pool12``), built at its first launch
+        self._pool12 = {}   # ... per form: from the composed tail (``FOLD_PRODUCTS``) or from the layers
 
     def collapses_b(self, mode: str = None) -> bool:
         """Whether chain B runs conv1 and TNet(64)'s conv1 as one per-cloud 12 -> 64 layer
@@ -721,6 +761,13 @@ class _Workspace:
         baseline; not NDNET_PN_FOLD_T2=chain, where chain C's prologue is what
         publishes them for chain D), and NDNET_PN_BACKBONE is not "chain"."""
         return BACKBONE == "pool12" and FOLD_T2_KERNEL and not self.W.baseline and self.mode in ("x6", "fp32")
+
+    def uses_tail(self) -> bool:
+        """Whether that launch starts from the fold's composed tail (``ndnet_pn_pool12_tail_run`` on
+        ``W.W23``, ``W.b23``): ``FOLD_PRODUCTS``, wherever ``uses_pool12`` holds.  Not with
+        NDNET_PN_COLLAPSE=0, which keeps the forward as it was before either change, launch for launch
+        and bit for bit."""
+        return bool(FOLD_PRODUCTS) and bool(COLLAPSE) and self.uses_pool12()
 
     def hip_layers(self, mode: str) -> list:
         """The chains' layers (A-D; A-C for a classification model) for ``_build_chain`` in one precision mode:
@@ -797,9 +844,10 @@ class _Workspace:
                 cc.fold_out_w, cc.fold_out_b = self.w1t2f.data_ptr(), self.b1t2.data_ptr()
         blk = structs[i]
         if i == 2 and self.uses_pool12():  # chain C collapsed to its 12 -> F layer: one launch in the chain's place
-            if self.pool12 is None:
-                self.pool12 = _Pool12(self)
-            blk = self.pool12
+            tail = self.uses_tail()
+            if tail not in self._pool12:
+                self._pool12[tail] = _Pool12(self, tail)
+            blk = self.pool12 = self._pool12[tail]
         if chain_timing is not None:  # torch events on the launch stream (bench.py)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -853,6 +901,12 @@ if BACKBONE not in ("pool12", "chain"):
 # "0" keeps the layered launches, bit for bit.  A module attribute read when a forward picks its
 # argument blocks, like BACKBONE.
 COLLAPSE = os.environ.get("NDNET_PN_COLLAPSE", "1") == "1"
+# Weight-only products formed by the fold (NDNET_FOLD_PROD jobs, re-run by every in-place re-fold) where
+# the forward formed them at every launch: "1" (default) runs chain C's 12 -> F launch from the composed
+# tail W23 = W2'^T W3'^T, b23 (ndnet_pn_pool12_tail_run) wherever ``_Workspace.uses_tail`` allows; "0"
+# keeps ndnet_pn_pool12_run, bit for bit.  A module attribute read when a forward picks its argument
+# blocks, like BACKBONE.
+FOLD_PRODUCTS = os.environ.get("NDNET_PN_FOLD_PRODUCTS", "1") == "1"
 # TNet(3)'s tail (fc3 + the t1 fold of conv1): "chain" (default) computes it in
 # chain B's prologue, per workgroup (ndnet_pn_chain.head_*: one launch and one
 # boundary fewer); "kernel" runs ndnet_pn_head3_run before chain B
