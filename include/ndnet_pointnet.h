@@ -151,6 +151,76 @@ int ndnet_pn_chain_run(const ndnet_pn_chain *args, int batch, void *stream);
  * would leave CUs idle, e.g. 16 clouds of 500 points. */
 int ndnet_pn_chain_run_t32(const ndnet_pn_chain *args, int batch, void *stream);
 
+/* The fp16 two-slice form of a chain's prec 1 layers ("x6" accuracy class on half the matrix
+ * instructions).  ndnet_pn_chain and ndnet_pn_layer are released structs of fixed size, so what the form
+ * adds travels in a block of its own beside them:
+ *   w16[l]      layer l's weights as two fp16 planes, [N/16][K/32][2 planes][64 lanes][8] -- the prec 1
+ *               layout with two planes per k-group -- holding h = fp16(W^T 2^s), l = fp16(W^T 2^s - h),
+ *               round to nearest even, with the layer-wide power of two 2^s that puts max |W^T| 2^s in
+ *               [2^13, 2^14) (s = 0 for an all-zero layer; s <= 100, see ndnet_pn_fold16_run); 16-byte
+ *               aligned.  NULL for a prec 0 layer.
+ *   scale[l]    DEVICE pointer to one float, 2^-s, written with w16[l] by ndnet_pn_fold16_run (the kernel
+ *               reads it at every launch: an in-place re-fold is followed with no host read)
+ *   fallbacks   DEVICE counter, incremented once per tile that ran the bf16 form instead (below)
+ * A producing epilogue stores split(16 v) as two fp16 planes (the layout, swizzle and pitch of the prec 2
+ * mode's h and m planes); the consuming epilogue undoes both scales with one exact multiply folded into
+ * the bias add, v = fma(acc, 2^-4 2^-s, bias), so pooled maxima and logits are true values.  Three
+ * products per operand pair (h h', h l', l h').  With 11 significant bits per slice and signed
+ * residuals, |x - h| <= 2^-11 |x| and |x - h - l| <= 2^-23 |x| (one bit short of fp32's 24 in the
+ * worst case, exact in half of them), so the dropped l l' is at most 2^-22 |x y|.
+ * fp16 has 5 exponent bits, so a tile (64 or 32 rows) takes this form only while every split layer's
+ * input lies in the window: the maximum |v| over the whole input tile in [2^-4, 2^11), or the tile all
+ * zero (then each element's representation error is at most max(2^-23 |v|, 2^-25 tile max); this relies
+ * on the f16 MFMA keeping subnormal inputs, which the default MODE.denorm does).  The maximum is gathered
+ * by the producing epilogue and tested, NaN and infinity counting as outside, after the layer barrier
+ * and before the chain's first global store or atomic; a tile outside it for any split layer is run
+ * again from the start by the unchanged bf16 three-slice code on L[l].w, so its result is bit for bit
+ * ndnet_pn_chain_run's.  Chain B's head prologue then publishes the same bits twice.
+ * ndnet_pn_chain_f16_run takes the chain block of ndnet_pn_chain_run (every split layer prec 1, its
+ * bf16 `w` valid) and this block.  NDNET_ERR_ARG (-20) before any launch, beyond ndnet_pn_chain_run's
+ * cases: ext or fallbacks NULL, a split layer of prec 2 or 3, a prec 1 layer whose w16 or scale is NULL
+ * or whose w16 is not 16-byte aligned or whose weights are per cloud, a split layer with fuse_next (a
+ * fused pair's first layer must be prec 0 here), a chain with no split layer, or a max-pooled chain
+ * whose last layer is fed by a fused one (its atomics would precede the test of its input). */
+typedef struct ndnet_pn_f16 {
+  const void *w16[NDNET_PN_MAX_LAYERS];
+  const float *scale[NDNET_PN_MAX_LAYERS];
+  uint32_t *fallbacks;
+} ndnet_pn_f16;
+int ndnet_pn_chain_f16_run(const ndnet_pn_chain *args, const ndnet_pn_f16 *ext, int batch, void *stream);
+int ndnet_pn_chain_f16_run_t32(const ndnet_pn_chain *args, const ndnet_pn_f16 *ext, int batch, void *stream);
+/* Reads a fallback counter and sets it to zero, after the work queued on `stream` so far (it waits for
+ * it: not graph-capturable).  Returns the count (clamped to INT32_MAX), -20 for NULL, -21 on a HIP error. */
+int ndnet_pn_take_f16_fallbacks(uint32_t *device_counter, void *stream);
+
+/* The fold of those fp16 planes, on the device from the live weights (re-run in place after a weight
+ * update, like ndnet_pn_fold_run; graph-capturable, no host read).  One job per layer, with the
+ * fields of ndnet_pn_fold_job's NDNET_FOLD_FRAG6 (fw(n, k), Kp % 32 == 0, Np % 16 == 0) and
+ *   out      the two fp16 planes (Kp * Np * 2 halves), 16-byte aligned
+ *   partial  16 floats of scratch: the launch's first kernel leaves the maxima of |fw| over 16
+ *            interleaved parts of the layer here (a pass of its own: the scale needs the whole layer)
+ *   scale    one float: 2^-s, s = min(13 - floor(log2(max |fw|)), 100): every finite maximum lands below
+ *            2^14 (s >= -114, which fp32 holds), one below 2^-87 stays under 2^13; s = 0 for a maximum
+ *            that is zero or not finite
+ * Two launches in stream order: the maxima, then the planes and the scale.  ndnet_pn_fold16_check
+ * validates a HOST copy of the list (NDNET_ERR_ARG for a NULL pointer, sizes that are not positive,
+ * ld < k0 + K, Kp < K, Np < N, Kp % 32, Np % 16, a misaligned out, BatchNorm pointers given in part)
+ * and returns the widest job's 8-element units in *max_units for ndnet_pn_fold16_run. */
+typedef struct ndnet_pn_fold16_job {
+  const float *w;
+  const float *gamma, *var;  /* BatchNorm1d weight and running variance; both NULL: none */
+  void *out;
+  float *partial;
+  float *scale;
+  int32_t N, K;
+  int32_t ld, k0;
+  int32_t Kp, Np;
+  float eps;
+  int32_t reserved;
+} ndnet_pn_fold16_job;
+int ndnet_pn_fold16_check(const ndnet_pn_fold16_job *host_jobs, int num_jobs, int64_t *max_units);
+int ndnet_pn_fold16_run(const ndnet_pn_fold16_job *device_jobs, int num_jobs, int64_t max_units, void *stream);
+
 /* Timing builds only (-DNDNET_PN_STAMPS, tools/pn_stamps.py): the
  * s_memrealtime stamps (100 MHz) of every workgroup of the last chain
  * launch, [wgs][16] (0 start, 1 head prologue, 2 input tile, 3 + l after

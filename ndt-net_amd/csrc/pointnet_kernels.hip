@@ -104,6 +104,8 @@ static_assert(kWaves % kRowBlocks == 0, "every row group has whole column groups
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline void atomic_max_f32(float* addr, float v) {
   v = v + 0.0f;  // -0 -> +0 so the integer orderings below agree
@@ -195,6 +197,7 @@ struct LayerCtx {
   const bf16x8* __restrict__ w6;   // split-bf16 fragments, offset by the lane (prec 1..3)
   const float* __restrict__ bias;
   int KG, N, relu, prec;           // KG: 16-row k-groups (prec 0) or 32-row (prec 1..3)
+  float sc;                        // the fp16 form (T = 2): what undoes the operands' scales, 2^-4 2^-s (1 for prec 0)
 };
 
 // bias: the layer's (this cloud's) bias, staged in LDS by the kernel's prologue
@@ -207,11 +210,19 @@ struct Pre {
   f32x4 r0, r1, r2;  // prec 1..3: bf16x8 planes h, m, l (bit_cast); prec 0: r0
 };
 
-__device__ inline LayerCtx layer_ctx(const ndnet_pn_chain& A, int l, int b, const float* bias) {
+template <int T>
+__device__ inline LayerCtx layer_ctx(const ndnet_pn_chain& A, const ndnet_pn_f16* X, int l, int b, const float* bias) {
   const ndnet_pn_layer& L = A.L[l];
   LayerCtx C;
   C.w = reinterpret_cast<const f32x4*>(L.w + (int64_t)b * L.w_cloud_stride) + (pn_tid() & 63);
   C.w6 = reinterpret_cast<const bf16x8*>(L.w + (int64_t)b * L.w_cloud_stride) + (pn_tid() & 63);
+  C.sc = 1.0f;
+  if constexpr (T == 2) {  // the fp16 planes (shared weights: no per-cloud copies) and the layer's scale
+    if (L.prec) {
+      C.w6 = reinterpret_cast<const bf16x8*>(X->w16[l]) + (pn_tid() & 63);
+      C.sc = 0.0625f * *X->scale[l];
+    }
+  }
   C.bias = bias;
   C.prec = L.prec;
   C.KG = L.prec ? L.K / 32 : L.K / 16;  // split-bf16: 32-row k-groups
@@ -321,10 +332,12 @@ __device__ __attribute__((always_inline)) inline void run_tiles(f32x4 (&acc)[RB]
 
 // Bias + ReLU of this wave's tile (rows row0.., bias columns col0 + 16 j + cl)
 // into an LDS activation region at columns oc0 + 16 j + cl.
-template <int RB, int NB>
+// T = 2 (the fp16 form): the accumulators carry the operands' scales, undone by sc in the bias add.
+template <int RB, int NB, int T = 6>
 __device__ __attribute__((always_inline)) inline void store_cols(const f32x4 (&acc)[RB][NB],
                                                                  const float* __restrict__ bias, int col0, int relu,
-                                                                 int row0, int out, int pout, int oc0) {
+                                                                 int row0, int out, int pout, int oc0, float sc = 1.0f) {
+  static_assert(T != 2 || NDNET_PN_SWAP, "the fp16 form is written for the swapped orientation");
   const int lane = pn_tid() & 63;
   const int kq = lane >> 4, cl = lane & 15;
 #if NDNET_PN_SWAP
@@ -338,7 +351,8 @@ __device__ __attribute__((always_inline)) inline void store_cols(const f32x4 (&a
       f32x4 v;
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        v[r] = acc[rb][j][r] + bv[r];
+        if constexpr (T == 2) v[r] = fmaf(acc[rb][j][r], sc, bv[r]);
+        else v[r] = acc[rb][j][r] + bv[r];
         if (relu) v[r] = fmaxf(v[r], 0.0f);
       }
       *reinterpret_cast<f32x4*>(g_smem + out + (row0 + 16 * rb + cl) * pout + oc0 + 16 * j + 4 * kq) = v;
@@ -362,10 +376,12 @@ __device__ __attribute__((always_inline)) inline void store_cols(const f32x4 (&a
 
 // Bias + ReLU + max over this wave's valid rows, one float atomic max per
 // column and wave into gmax (the workgroup's row groups meet in the atomics).
-template <int RB, int NB>
+// T = 2: the maximum is taken over the scaled accumulators and sc (a positive power of two) undone in
+// the bias add -- fma(a, sc, b) is monotonic in a too.
+template <int RB, int NB, int T = 6>
 __device__ __attribute__((always_inline)) inline void pool_cols(const f32x4 (&acc)[RB][NB],
                                                                 const float* __restrict__ bias, int col0, int relu,
-                                                                int row0, int rows_valid, float* gmax) {
+                                                                int row0, int rows_valid, float* gmax, float sc = 1.0f) {
   const int lane = pn_tid() & 63;
   const int kq = lane >> 4, cl = lane & 15;
 #if NDNET_PN_SWAP
@@ -397,7 +413,9 @@ __device__ __attribute__((always_inline)) inline void pool_cols(const f32x4 (&ac
     }
     const float mm = cl == 0 ? m[0] : cl == 1 ? m[1] : cl == 2 ? m[2] : m[3];
     if (cl < 4 && mm > -INFINITY) {
-      float v = mm + bias[col0 + 16 * j + 4 * kq + cl];
+      float v;
+      if constexpr (T == 2) v = fmaf(mm, sc, bias[col0 + 16 * j + 4 * kq + cl]);
+      else v = mm + bias[col0 + 16 * j + 4 * kq + cl];
       if (relu) v = fmaxf(v, 0.0f);
       atomic_max_f32(gmax + col0 + 16 * j + 4 * kq + cl, v);
     }
@@ -461,14 +479,51 @@ __device__ inline void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
 // A plane a mode does not read is neither computed, stored, loaded from LDS
 // or global memory, nor prefetched; the LDS layout (plane p at p * kP * pitch)
 // and the weight layout (three planes per k-group) are the same in all modes.
+//
+// T = 2 is the fp16 two-slice form of the same layers (ndnet_pn_f16, include/ndnet_pointnet.h): operands
+// x = h + l in two fp16 (11 + 11 significant bits and the residual's sign), three products l*h, h*l, h*h
+// on v_mfma_f32_16x16x32_f16 -- T = 3's instruction shape with T = 6's accuracy class.  fp16's 5 exponent
+// bits make it conditional: activations are stored as split(16 v), weights as split(w 2^s) (two planes
+// per k-group, a layout of their own), the epilogue undoes both scales, and a tile whose activations
+// leave the window runs T = 6 instead (k_pn_chain_f16).  The planes are moved as bf16x8 / bf16x4 bit
+// patterns; only the conversions and the MFMA know the element type.
 template <int T>
-constexpr int kPlanes = T == 6 ? 3 : T == 3 ? 2 : 1;
+constexpr int kPlanes = T == 6 ? 3 : T == 1 ? 1 : 2;
+// planes stored per k-group of the weights a mode reads
+template <int T>
+constexpr int kWPlanes = T == 2 ? 2 : 3;
+
+// the row maximum of a lane row of 16 (DPP), on bit patterns: NaN and infinity order above every finite |v|
+__device__ inline unsigned umax_row16(unsigned x) {
+  int v = (int)x;
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+  v = max(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, false));  // row_mirror
+  return (unsigned)v;
+}
+
+// T = 2: |v|'s bits (sign cleared, so they order as the values do) of everything a lane stored into a
+// split layer's input, folded into that tensor's window word: one LDS max per lane row
+__device__ inline void window_note(int flag, unsigned mx) {
+  mx = umax_row16(mx);
+  if ((pn_tid() & 15) == 0) atomicMax(reinterpret_cast<unsigned*>(g_smem) + flag, mx);
+}
+
+// split(16 v) into two fp16, both conversions to nearest even (v_cvt_f16_f32)
+__device__ inline void split_f16(float v, _Float16& h, _Float16& l) {
+  const float s = 16.0f * v;
+  h = (_Float16)s;
+  l = (_Float16)(s - (float)h);
+}
 
 // v's first kPlanes<T> bf16 planes (l, or m and l, left alone when unused)
 template <int T>
 __device__ inline void split_t(float v, __bf16& h, __bf16& m, __bf16& l) {
-  static_assert(T == 6 || T == 3 || T == 1, "6, 3 or 1 terms");
-  if constexpr (T == 6) {
+  static_assert(T == 6 || T == 3 || T == 2 || T == 1, "6, 3 or 1 terms (2: the fp16 form, which has split_f16)");
+  if constexpr (T == 2) {
+    __builtin_unreachable();  // its callers return before they get here
+  } else if constexpr (T == 6) {
     split3(v, h, m, l);
   } else if constexpr (T == 3) {
     h = (__bf16)v;
@@ -484,13 +539,42 @@ template <int RB, int NB, int T>
 __device__ __attribute__((always_inline)) inline void store_cols_planes(const f32x4 (&acc)[RB][NB],
                                                                         const float* __restrict__ bias, int col0,
                                                                         int relu, int row0, int out, int pitchb,
-                                                                        int oc0) {
+                                                                        int oc0, float sc = 1.0f, int flag = 0) {
   const int lane = pn_tid() & 63;
   const int kq = lane >> 4, cl = lane & 15;
   __bf16* const base = reinterpret_cast<__bf16*>(g_smem + out);
   const int plane = kP * pitchb;
 #if NDNET_PN_SWAP
   typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+  if constexpr (T == 2) {  // two fp16 planes of split(16 v), v = fma(acc, sc, bias); the window word takes max |v|
+    unsigned mx = 0;
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      float bv[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) bv[r] = bias[col0 + 16 * j + 4 * kq + r];
+#pragma unroll
+      for (int rb = 0; rb < RB; rb++) {
+        f16x4 h4, l4;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          float v = fmaf(acc[rb][j][r], sc, bv[r]);
+          if (relu) v = fmaxf(v, 0.0f);
+          mx = max(mx, __float_as_uint(v) & 0x7fffffffu);
+          _Float16 h, l;
+          split_f16(v, h, l);
+          h4[r] = h;
+          l4[r] = l;
+        }
+        const int row = row0 + 16 * rb + cl;
+        const int e = row * pitchb + plane_col(row, oc0 + 16 * j + 4 * kq);
+        *reinterpret_cast<f16x4*>(base + e) = h4;
+        *reinterpret_cast<f16x4*>(base + plane + e) = l4;
+      }
+    }
+    window_note(flag, mx);
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < NB; j++) {
     float bv[4];
@@ -555,7 +639,11 @@ __device__ __attribute__((always_inline)) inline void mma_kgroup_x6(f32x4 (&acc)
 #pragma unroll
       for (int j = 0; j < NB; j++)
 #if NDNET_PN_SWAP
-        acc[rb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[j][pb], a[rb], acc[rb][j], 0, 0, 0);
+        if constexpr (T == 2)
+          acc[rb][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bw[j][pb]),
+                                                              __builtin_bit_cast(f16x8, a[rb]), acc[rb][j], 0, 0, 0);
+        else
+          acc[rb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[j][pb], a[rb], acc[rb][j], 0, 0, 0);
 #else
         acc[rb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rb], bw[j][pb], acc[rb][j], 0, 0, 0);
 #endif
@@ -570,8 +658,8 @@ __device__ __attribute__((always_inline)) inline void mma_kgroup_x6(f32x4 (&acc)
     mm(2);
     mm(1);
     mm(0);
-  } else if constexpr (T == 3) {
-    ld(1);  // m: m*h
+  } else if constexpr (T == 3 || T == 2) {
+    ld(1);  // m: m*h  (T = 2: the fp16 l plane, l*h)
     mm(0);
     ld(0);  // h: h*m, h*h
     mm(1);
@@ -598,10 +686,11 @@ __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[
   // sums are unchanged
   const int NT = nchunk * nkg;  // k-group steps
   const int plane = kP * pitchb;
-  const int64_t jstride = (int64_t)KG * 3 * 64;
-  const int64_t chunk_jump = ((int64_t)cbs * KG - (nkg - 1)) * 3 * 64;
-  const int64_t wrap = (int64_t)nchunk * cbs * KG * 3 * 64;
-  const bf16x8* lp = w + ((int64_t)(cb0 + rot * cbs) * KG + kg0) * 3 * 64;
+  constexpr int WPL = kWPlanes<T>;  // planes stored per k-group (3; the fp16 form's 2)
+  const int64_t jstride = (int64_t)KG * WPL * 64;
+  const int64_t chunk_jump = ((int64_t)cbs * KG - (nkg - 1)) * WPL * 64;
+  const int64_t wrap = (int64_t)nchunk * cbs * KG * WPL * 64;
+  const bf16x8* lp = w + ((int64_t)(cb0 + rot * cbs) * KG + kg0) * WPL * 64;
   int lkk = 0, lleft = NT, lc = rot;
   auto advance = [&]() {
     if (lleft > 1) {
@@ -614,7 +703,7 @@ __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[
           lp -= wrap;
         }
       } else {
-        lp += 3 * 64;
+        lp += WPL * 64;
       }
     }
   };
@@ -662,7 +751,7 @@ __device__ __attribute__((always_inline)) inline void run_tiles_x6(f32x4 (&acc)[
 // 4 RB column groups of waves; N in chunks of (column groups x NB x 16).
 template <int RB, int NB, int T>
 __device__ __attribute__((always_inline)) inline void plain_layer(const LayerCtx& C, int in, int pin, int out, int pout, float* gmax, int rows_valid,
-                            bool out_planes, Pre pre = {}) {
+                            bool out_planes, Pre pre = {}, int oflag = 0) {
   constexpr int WR = kRowBlocks / RB, WC = kWaves / WR, CB = WC * NB;
   const int lane = pn_tid() & 63, wave = pn_tid() >> 6;
   const int wr = wave / WC, wc = wave % WC;
@@ -675,9 +764,9 @@ __device__ __attribute__((always_inline)) inline void plain_layer(const LayerCtx
   zero_acc(acc);
   auto epi = [&](f32x4 (&a)[RB][NB], int c) {
     const int col0 = (c * CB + wc * NB) * 16;
-    if (gmax) pool_cols<RB, NB>(a, C.bias, col0, C.relu, row0, rows_valid, gmax);
-    else if (out_planes) store_cols_planes<RB, NB, T>(a, C.bias, col0, C.relu, row0, out, C.N + kPadB, col0);
-    else store_cols<RB, NB>(a, C.bias, col0, C.relu, row0, out, pout, col0);
+    if (gmax) pool_cols<RB, NB, T>(a, C.bias, col0, C.relu, row0, rows_valid, gmax, C.sc);
+    else if (out_planes) store_cols_planes<RB, NB, T>(a, C.bias, col0, C.relu, row0, out, C.N + kPadB, col0, C.sc, oflag);
+    else store_cols<RB, NB, T>(a, C.bias, col0, C.relu, row0, out, pout, col0, C.sc);
     zero_acc(a);
   };
   const int nchunk = C.N < CB * 16 ? 1 : C.N / (CB * 16);
@@ -713,7 +802,7 @@ __host__ __device__ inline int fbuf_floats(int qprec) {
 // activation never needs LDS of its own.  One barrier per chunk.
 template <int RB, int NB, int T>
 __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx& P, const LayerCtx& Q, int in, int pin, int fbuf, int out, int pout,
-                           float* gmax, int rows_valid, bool out_planes, Pre pre = {}) {
+                           float* gmax, int rows_valid, bool out_planes, Pre pre = {}, int qflag = 0, int oflag = 0) {
   constexpr int kFP = kFuseNC + kPadF;
   constexpr int WR = kRowBlocks / RB, WC = kWaves / WR;
   const int lane = pn_tid() & 63, wave = pn_tid() >> 6;
@@ -735,8 +824,8 @@ __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx&
     zero_acc(acc1);
     const int fb = fbuf + (f & 1) * fbsz;
     auto epi = [&](f32x4 (&a)[1][PNB], int) {
-      if (Q.prec) store_cols_planes<1, PNB, T>(a, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fb, kFuseNC + kPadB, 16 * pwc);
-      else store_cols<1, PNB>(a, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fb, kFP, 16 * pwc);
+      if (Q.prec) store_cols_planes<1, PNB, T>(a, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fb, kFuseNC + kPadB, 16 * pwc, P.sc, qflag);
+      else store_cols<1, PNB, T>(a, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fb, kFP, 16 * pwc, P.sc);
     };
     Pre pf = pre;
     if (f != 0) pf.on = false;
@@ -763,9 +852,9 @@ __device__ __attribute__((always_inline)) inline void fused_pair(const LayerCtx&
     __syncthreads();
   }
   if (qidle) return;
-  if (gmax) pool_cols<RB, NB>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, rows_valid, gmax);
-  else if (out_planes) store_cols_planes<RB, NB, T>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc * NB);
-  else store_cols<RB, NB>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, out, pout, 16 * qwc * NB);
+  if (gmax) pool_cols<RB, NB, T>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, rows_valid, gmax, Q.sc);
+  else if (out_planes) store_cols_planes<RB, NB, T>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc * NB, Q.sc, oflag);
+  else store_cols<RB, NB, T>(acc2, Q.bias, 16 * qwc * NB, Q.relu, qrow0, out, pout, 16 * qwc * NB, Q.sc);
 }
 
 // The fused pair with both layers split-bf16 and P's K = 64 (the seg head's
@@ -789,7 +878,8 @@ template <int RB, int T, bool PF32 = false>
 __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const LayerCtx& P, const LayerCtx& Q, int in,
                                                                      int fbuf, int out, int pout, float* gmax,
                                                                      int rows_valid, bool out_planes,
-                                                                     f32x4 xa = {0.f, 0.f, 0.f, 0.f}) {
+                                                                     f32x4 xa = {0.f, 0.f, 0.f, 0.f}, int qflag = 0,
+                                                                     int oflag = 0) {
   constexpr int WR = kRowBlocks / RB, WC = kWaves / WR;  // Q: NB = 1
   constexpr int PWC = kWaves / kRowBlocks;                // P: 4 column groups of one block
   static_assert(PWC == 4 && kFuseNC == 64, "16 waves, 64-column chunks");
@@ -803,7 +893,8 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
   const int fbsz = fbuf_floats(1) / 2;
   constexpr int fpb = kFuseNC + kPadB;
   // chunk f's weights: P column block 4 f + pwc, k-groups 0, 1; Q column block qwc, k-groups 2 f, 2 f + 1
-  constexpr int NPL = kPlanes<T>;  // of the three planes stored per k-group
+  constexpr int NPL = kPlanes<T>;  // of the three planes stored per k-group (the fp16 form: both of its two)
+  constexpr int WPL = kWPlanes<T>;
   bf16x8 wp[2][1][NPL], wq[2][1][NPL];
   f32x4 wpf[1];  // PF32: chunk f's fragment of P (one k-group)
   auto load_p = [&](int f) {
@@ -811,18 +902,18 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
       wpf[0] = P.w[(int64_t)(4 * f + pwc) * 64];
       return;
     }
-    const bf16x8* s = P.w6 + ((int64_t)(4 * f + pwc) * P.KG) * 3 * 64;
+    const bf16x8* s = P.w6 + ((int64_t)(4 * f + pwc) * P.KG) * WPL * 64;
 #pragma unroll
     for (int k = 0; k < 2; k++)
 #pragma unroll
-      for (int p = 0; p < NPL; p++) wp[k][0][p] = s[(k * 3 + p) * 64];
+      for (int p = 0; p < NPL; p++) wp[k][0][p] = s[(k * WPL + p) * 64];
   };
   auto load_q = [&](int f) {
-    const bf16x8* s = Q.w6 + ((int64_t)qwc * Q.KG + 2 * f) * 3 * 64;
+    const bf16x8* s = Q.w6 + ((int64_t)qwc * Q.KG + 2 * f) * WPL * 64;
 #pragma unroll
     for (int k = 0; k < 2; k++)
 #pragma unroll
-      for (int p = 0; p < NPL; p++) wq[k][0][p] = s[(k * 3 + p) * 64];
+      for (int p = 0; p < NPL; p++) wq[k][0][p] = s[(k * WPL + p) * 64];
   };
   auto p_chunk = [&](int f) {
     f32x4 acc1[1][1];
@@ -834,7 +925,8 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
 #pragma unroll
       for (int k = 0; k < 2; k++) mma_kgroup_x6<1, 1, T>(acc1, ain6 + 32 * k, kP * pinb, 16 * pinb, wp[k]);
     }
-    store_cols_planes<1, 1, T>(acc1, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fbuf + (f & 1) * fbsz, fpb, 16 * pwc);
+    store_cols_planes<1, 1, T>(acc1, P.bias, 64 * f + 16 * pwc, P.relu, prow0, fbuf + (f & 1) * fbsz, fpb, 16 * pwc, P.sc,
+                               qflag);
   };
   f32x4 acc2[RB][1];
   zero_acc(acc2);
@@ -868,9 +960,9 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
 #endif
     __syncthreads();
   }
-  if (gmax) pool_cols<RB, 1>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, rows_valid, gmax);
-  else if (out_planes) store_cols_planes<RB, 1, T>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc);
-  else store_cols<RB, 1>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, out, pout, 16 * qwc);
+  if (gmax) pool_cols<RB, 1, T>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, rows_valid, gmax, Q.sc);
+  else if (out_planes) store_cols_planes<RB, 1, T>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, out, Q.N + kPadB, 16 * qwc, Q.sc, oflag);
+  else store_cols<RB, 1, T>(acc2, Q.bias, 16 * qwc, Q.relu, qrow0, out, pout, 16 * qwc, Q.sc);
 }
 
 // Loads the first weight step this wave runs in layer l (the 16-wave 64-point
@@ -880,6 +972,7 @@ __device__ __attribute__((always_inline)) inline void fused_pair_x6p(const Layer
 template <int T>
 __device__ inline void prefetch_first(const ndnet_pn_chain& A, int l, int b, Pre& pre) {
   pre.on = false;
+  if constexpr (T == 2) return;  // (the experiment below addresses three planes per k-group)
 #ifndef NDNET_PN_PREFETCH  // off by default: measured 1-2 us slower per chain (profiles/r03e_stamps_ab.txt)
   return;
 #endif
@@ -963,397 +1056,45 @@ __host__ __device__ inline int region0_floats(const ndnet_pn_chain& A, int plane
   return valu_layer0(A) && r < kValu0Floats + 16 ? kValu0Floats + 16 : r;
 }
 
+// The kernel's body, one tile from its first load to its stores.  T = 2 is the fp16 form (X: its planes
+// and scales; flag_base: NDNET_PN_MAX_LAYERS LDS words, word l the maximum |v| of split layer l's input
+// tile, gathered by the epilogue that stores it): it tests each split layer's input after the barrier
+// that closes its producer and returns false -- the whole workgroup, before the chain's first global
+// store or atomic other than the head prologue's -- when one lies outside the window; the caller then
+// runs the tile through T = 6.  Every other T returns true.
+template <int T>
+__device__ __attribute__((always_inline)) inline bool pn_chain_body(const ndnet_pn_chain& A, const ndnet_pn_f16* X,
+                                                                    int planes, int fbuf, int bias_base,
+                                                                    int flag_base) {
+#define PN_BODY_FAIL return false
+#include "pointnet_chain_body.inc"
+#undef PN_BODY_FAIL
+  return true;
+}
+
 // One instantiation per mode of the chain's split-bf16 layers (T terms):
 // k_pn_chain<6> serves prec 1 and chains with no split layer -- the kernel as
 // it was before the modes, register for register -- <3> prec 2, <1> prec 3.
 template <int T>
 __global__ void __launch_bounds__(kThreads) k_pn_chain(ndnet_pn_chain A, int planes, int fbuf, int bias_base) {
-  const int b = blockIdx.y;
-  const int p0 = blockIdx.x * kP;
-  PN_STAMP(0);
-  // LDS: activation region 0 | region 1 | [fused-chunk double buffer] | biases of layers 1..
-  const int pitch0 = A.max_width + kPadF, pitch1 = A.max_width2 + kPadF;
-  const int reg[2] = {0, region0_floats(A, planes)};
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // every layer's bias (this cloud's) -> LDS at boff[l] (layer 0's into the
-  // prologue scratch when it runs on the VALU); the loads are issued together
-  // with the prologue's, so the epilogues never wait on a global bias read
-  int boff[NDNET_PN_MAX_LAYERS];
-  {
-    int o = bias_base;
-#pragma unroll
-    for (int l = 0; l < NDNET_PN_MAX_LAYERS; l++) {
-      boff[l] = o;
-      if (l < A.num_layers) o += A.L[l].N;
-    }
-    float bv[NDNET_PN_MAX_LAYERS][2];
-#pragma unroll
-    for (int l = 0; l < NDNET_PN_MAX_LAYERS; l++)
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const int e = threadIdx.x + i * kThreads;
-        bv[l][i] = (l < A.num_layers && e < A.L[l].N) ? A.L[l].bias[(int64_t)b * A.L[l].bias_cloud_stride + e] : 0.0f;
-      }
-#pragma unroll
-    for (int l = 0; l < NDNET_PN_MAX_LAYERS; l++)
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const int e = threadIdx.x + i * kThreads;
-        if (l < A.num_layers && e < A.L[l].N) g_smem[boff[l] + e] = bv[l][i];
-      }
-  }
-  const bool v0 = valu_layer0(A);
-  Pre pre;  // the next layer's first weight step (prefetched before each layer barrier)
-  prefetch_first<T>(A, v0 ? 1 : 0, b, pre);
-  float* const s_w0 = g_smem;  // v0: W0^T [16][64] row-major, in region 0
-  // v0: this thread's point rows (t / 16 + pass * kThreads / 16) and 4 output
-  // channels (4 (t % 16) ..)
-  constexpr int kV0Pass = kP * 16 / kThreads;
-  static_assert(kV0Pass >= 1 && kV0Pass * kThreads == kP * 16, "whole layer-0 passes");
-  const int vq = threadIdx.x & 15;
-  f32x4 xin[kV0Pass][3] = {};
-  // both prologues (chain B collapsed): the fold matrix is no product of this launch's head, so waves
-  // 0..3, which run the fold, load their B operands of its 16 MFMA steps here with the kernel's first
-  // loads -- M[4 st + fk][16 wave + fr], no LDS staging -- and they land under the head prologue's two
-  // round trips
-  const bool fold_early = A.head_h2 && A.fold_t2;
-  constexpr int kFoldPitch = 68;  // floats per row of the head's W1f copy the fold reads: 16 rows x 4 k on 64 distinct banks
-  float fmr[16] = {};
-  if (fold_early && wave < 4) {
-    const float* mb = A.fold_t2 + (int64_t)b * A.fold_ld + (lane >> 4) * 64 + 16 * wave + (lane & 15);
-#pragma unroll
-    for (int st = 0; st < 16; st++) fmr[st] = mb[st * 256];
-  }
-  // ... and the folded layer's own bias (TNet(64) conv1's), joined to b0' by waves 0..3: column 16 wave + (lane & 15)
-  const float fb = A.fold_bias ? A.fold_bias[(16 * wave + (lane & 15)) & 63] : 0.0f;
-  // a chain that opens with the direct fused pair: this lane's piece of its input row, P's A operand for
-  // every chunk (row (wave / 4) * 16 + cl, columns 4 kq ..; zero past in_cols and past the cloud)
-  const bool direct0 = pair0_direct(A);
-  f32x4 xa = {0.f, 0.f, 0.f, 0.f};
-  if (direct0) {
-    const int kq = lane >> 4, p = p0 + (wave / 4) * 16 + (lane & 15);
-    if (p < A.num_points && 4 * kq < A.in_cols) {
-      xa = *reinterpret_cast<const f32x4*>(A.x + ((int64_t)b * A.num_points + p) * A.x_ld + 4 * kq);
-#pragma unroll
-      for (int s = 0; s < 4; s++) {
-        if (4 * kq + s >= A.in_cols) xa[s] = 0.0f;
-        else if (A.x_nonfinite_nan && !(fabsf(xa[s]) < INFINITY)) xa[s] = NAN;
-      }
-    }
-  }
-  if (v0) {
-#pragma unroll
-    for (int ps = 0; ps < kV0Pass; ps++) {
-      const int vr = (threadIdx.x >> 4) + ps * (kThreads / 16);
-      const int p = p0 + vr;
-      if (p < A.num_points) {
-        const f32x4* xr = reinterpret_cast<const f32x4*>(A.x + ((int64_t)b * A.num_points + p) * A.x_ld);
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-          if (4 * i < A.in_cols) xin[ps][i] = xr[i];
-      }
-    }
-    if (!A.head_h2 && threadIdx.x < 256) {  // W0^T fragment-major [cb][kq][cl][s] -> row-major [k][n]
-      const f32x4 wv = reinterpret_cast<const f32x4*>(A.L[0].w + (int64_t)b * A.L[0].w_cloud_stride)[threadIdx.x];
-      const int cb = threadIdx.x >> 6, kq = (threadIdx.x >> 4) & 3, cl = threadIdx.x & 15;
-#pragma unroll
-      for (int s = 0; s < 4; s++) s_w0[(4 * kq + s) * 64 + 16 * cb + cl] = wv[s];
-    }
-  }
-  if (A.head_h2) {
-    // TNet(3)'s tail for this cloud (ndnet_pn_head3_run's work, ndtnet.py:57-60):
-    // t1 = h2 @ W3^T + b3, then conv1 with t1 folded into layer 0's weights
-    float* const s_t1 = g_smem + (v0 ? kValu0Floats : 0);  // [9] (v0: past the scratch; region 0 is free until layer 1)
-    const int M = A.head_kin * A.head_nout, total = 16 * A.head_nout;  // one k-group, K padded to 16
-    // this thread's fold element(s): basis values loaded ahead of the fc3 reduction
-    const int e0 = threadIdx.x;
-    const int cb0 = e0 >> 8, ln0 = (e0 >> 2) & 63, k0 = 4 * (ln0 >> 4) + (e0 & 3), n0 = 16 * cb0 + (ln0 & 15);
-    float bas[9];
-#pragma unroll
-    for (int a = 0; a < 9; a++) bas[a] = (e0 < total && k0 < A.head_kin) ? A.head_basis[a * M + k0 * A.head_nout + n0] : 0.0f;
-    const float* h = A.head_h2 + (int64_t)b * A.head_ld;
-    for (int o = wave; o < 9; o += kWaves) {  // one wave per output, lanes split K
-      float acc = 0.0f;
-      const float* wr = A.head_w3 + (int64_t)o * A.head_K;
-      if (A.head_K == 256) {  // one float4 of h and of the row per lane: one load round trip
-        const f32x4 hv = reinterpret_cast<const f32x4*>(h)[lane];
-        const f32x4 wv = reinterpret_cast<const f32x4*>(wr)[lane];
-        acc = (hv[0] * wv[0] + hv[1] * wv[1]) + (hv[2] * wv[2] + hv[3] * wv[3]);
-      } else {
-        for (int k = lane; k < A.head_K; k += 64) acc += h[k] * wr[k];
-      }
-      for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-      if (lane == 0) {
-        s_t1[o] = acc + A.head_b3[o];
-        if (blockIdx.x == 0) A.head_t1[b * 9 + o] = acc + A.head_b3[o];
-      }
-    }
-    __syncthreads();
-    float* w1 = const_cast<float*>(A.L[0].w) + (int64_t)b * A.L[0].w_cloud_stride;
-    // v0: only the cloud's first workgroup publishes the fragment-major W0^T
-    // (chains C and D read it in later launches); every workgroup keeps its own
-    // copy in LDS.  Otherwise every workgroup stores it and its layer 0 reads it.
-    const bool publish = !v0 || blockIdx.x == 0;
-    for (int e = e0; e < total; e += kThreads) {
-      const int cb = e >> 8, ln = (e >> 2) & 63, k = 4 * (ln >> 4) + (e & 3), n = 16 * cb + (ln & 15);
-      float acc = 0.0f;
-      if (e == e0) {
-#pragma unroll
-        for (int a = 0; a < 9; a++) acc += s_t1[a] * bas[a];
-      } else if (k < A.head_kin) {
-#pragma unroll
-        for (int a = 0; a < 9; a++) acc += s_t1[a] * A.head_basis[a * M + k * A.head_nout + n];
-      }
-      if (publish) w1[e] = acc;
-      // the fold prologue follows: its A operand [W1f; b1; 0] goes to region 1 at a pitch its reads do
-      // not conflict on, and s_w0 is left to its output (no barrier between its MFMAs and its stores)
-      if (fold_early) g_smem[reg[1] + k * kFoldPitch + n] = k == 12 ? g_smem[boff[0] + n] : acc;
-      else if (v0) s_w0[k * 64 + n] = acc;
-    }
-    // !v0: layer 0 reads these weights back: __syncthreads' workgroup-scope release
-    // / acquire orders this workgroup's stores before its loads (same CU; no
-    // lines of them are cached here yet).  Every workgroup of the cloud stores
-    // the same bits.  (A device-scope __threadfence here writes back the L2:
-    // measured +60 us per launch.)
-    PN_STAMP(1);
-  }
-  if (A.fold_t2) {
-    // TNet(64)'s transform through layer 0 (chains C, D; v0 only, checked on
-    // the host): x_t2 = t2^T (W0 x + b0) = (W0^T t2)^T x + t2^T b0, so layer 0
-    // runs on W0' = W0^T t2 (its 12 used rows) and b0' = b0^T t2: a 16 x 64 x 64
-    // GEMM (rows 0..11 W0^T, row 12 the bias, 13..15 zero) on the fp32 MFMA,
-    // waves 0..3 one 16-column block each, t2 staged in region 1 (layer 0 has
-    // not written it yet; the launcher keeps the biases past it)
-    // After the head prologue (chain B collapsed: a shared matrix, hot in L2) the same product takes
-    // its B operand from registers (fmr) and its A operand from the head's copy in region 1, so the
-    // fold costs one barrier and 16 MFMAs of four waves.
-    float* const s_t2 = g_smem + reg[1];
-    f32x4 fo = {0.f, 0.f, 0.f, 0.f};
-    const int fr = lane & 15, fk = lane >> 4;  // operand row / k within a 4-step
-    if (fold_early) {
-      __syncthreads();  // [W1f; b1; 0] at s_t2, pitch kFoldPitch
-      if (wave < 4) {
-#pragma unroll
-        for (int st = 0; st < 16; st++)
-          fo = __builtin_amdgcn_mfma_f32_16x16x4f32(s_t2[fr * kFoldPitch + 4 * st + fk], fmr[st], fo, 0, 0, 0);
-      }
-    } else {
-      const f32x4* t2b = reinterpret_cast<const f32x4*>(A.fold_t2 + (int64_t)b * A.fold_ld);
-      for (int e = threadIdx.x; e < 1024; e += kThreads) reinterpret_cast<f32x4*>(s_t2)[e] = t2b[e];
-      __syncthreads();  // + s_w0 (W0^T row-major) and layer 0's bias at boff[0]
-      if (wave < 4) {
-#pragma unroll
-        for (int st = 0; st < 16; st++) {
-          const int i = 4 * st + fk;
-          const float av = fr < 12 ? s_w0[fr * 64 + i] : fr == 12 ? g_smem[boff[0] + i] : 0.0f;
-          const float bv = s_t2[i * 64 + 16 * wave + fr];
-          fo = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, fo, 0, 0, 0);
-        }
-      }
-      __syncthreads();
-    }
-    if (wave < 4) {  // lane (fk, fr): rows 4 fk + r, column 16 wave + fr
-      const int n = 16 * wave + fr;
-      if (A.fold_bias && fk == 3) fo[0] += fb;  // row 12: b0' = b0^T M + the folded layer's bias
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int row = 4 * fk + r;
-        if (row < 12) s_w0[row * 64 + n] = fo[r];
-        else if (row == 12) g_smem[boff[0] + n] = fo[r];
-      }
-      // the cloud's first workgroup publishes W0' (fragment-major, K = 16, rows
-      // 12..15 left zero) and b0' for a later chain's plain layer 0 (chain D)
-      if (A.fold_out_w && blockIdx.x == 0) {
-        float* ow = A.fold_out_w + (int64_t)b * 1024;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int row = 4 * fk + r;
-          if (row < 12) ow[(((n >> 4) * 64 + ((row >> 2) & 3) * 16 + (n & 15)) << 2) + (row & 3)] = fo[r];
-          else if (row == 12) A.fold_out_b[(int64_t)b * 64 + n] = fo[r];
-        }
-      }
-    }
-    PN_STAMP(1);  // (timing builds) chains C / D: t2 staged and folded into layer 0
-  }
-  __syncthreads();
-  if (v0) {
-    // layer 0: out = act(x W0^T + b0) for 4 channels of one point, into region 1
-    // as the next layer reads it (three bf16 planes, or fp32)
-#pragma unroll
-    for (int ps = 0; ps < kV0Pass; ps++) {
-      const int vr = (threadIdx.x >> 4) + ps * (kThreads / 16);
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      float xs[12] = {xin[ps][0][0], xin[ps][0][1], xin[ps][0][2], xin[ps][0][3], xin[ps][1][0], xin[ps][1][1],
-                      xin[ps][1][2], xin[ps][1][3], xin[ps][2][0], xin[ps][2][1], xin[ps][2][2], xin[ps][2][3]};
-      if (A.x_nonfinite_nan) {  // a collapsed first layer: the row leaves its ReLU as zeros, as the layered pair's does
-#pragma unroll
-        for (int k = 0; k < 12; k++) xs[k] = fabsf(xs[k]) < INFINITY ? xs[k] : NAN;
-      }
-#pragma unroll
-      for (int k = 0; k < 12; k++) {
-        if (k < A.in_cols) {
-          const f32x4 w = *reinterpret_cast<const f32x4*>(s_w0 + k * 64 + 4 * vq);
-#pragma unroll
-          for (int j = 0; j < 4; j++) acc[j] = fmaf(xs[k], w[j], acc[j]);
-        }
-      }
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(g_smem + boff[0] + 4 * vq);
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        acc[j] += bb[j];
-        if (A.L[0].relu) acc[j] = fmaxf(acc[j], 0.0f);
-      }
-      const int out = reg[1];
-      if (A.L[1].prec) {  // the mode's bf16 planes, pitch 64 + kPadB
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        const int pb = 64 + kPadB;
-        __bf16* const base = reinterpret_cast<__bf16*>(g_smem + out) + vr * pb + plane_col(vr, 4 * vq);
-        bf16x4 h4, m4, l4;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          __bf16 hh, mm, ll;
-          split_t<T>(acc[j], hh, mm, ll);
-          h4[j] = hh;
-          if constexpr (T >= 3) m4[j] = mm;
-          if constexpr (T == 6) l4[j] = ll;
-        }
-        *reinterpret_cast<bf16x4*>(base) = h4;
-        if constexpr (T >= 3) *reinterpret_cast<bf16x4*>(base + kP * pb) = m4;
-        if constexpr (T == 6) *reinterpret_cast<bf16x4*>(base + 2 * kP * pb) = l4;
-      } else {
-        *reinterpret_cast<f32x4*>(g_smem + out + vr * pitch1 + 4 * vq) = acc;
-      }
-    }
-  } else if (!direct0) {
-    const int K0 = A.L[0].K;
-    for (int e = threadIdx.x; e < kP * K0; e += kThreads) {
-      const int r = e / K0, c = e % K0;
-      const int p = p0 + r;
-      float v = 0.0f;
-      if (p < A.num_points && c < A.in_cols) v = A.x[((int64_t)b * A.num_points + p) * A.x_ld + c];
-      if (A.x_nonfinite_nan && !(fabsf(v) < INFINITY)) v = NAN;
-      g_smem[r * pitch0 + c] = v;
-    }
-  }
-  __syncthreads();
-  PN_STAMP(2);
-  const int rows_valid = A.num_points - p0;
-  float* const gmax_b = A.mode == 0 ? A.gmax + (int64_t)b * A.gmax_ld : nullptr;
-  int lfirst = v0 ? 1 : 0;
-  if constexpr (kP == 64 && kWaves == 16) {
-    if (direct0) {  // layers 0 and 1 as the direct fused pair, ahead of the loop: xa is live up to here only
-      const LayerCtx P = layer_ctx(A, 0, b, g_smem + boff[0]), Q = layer_ctx(A, 1, b, g_smem + boff[1]);
-      const bool last = A.num_layers == 2;
-      fused_pair_x6p<4, T, true>(P, Q, reg[0], fbuf, reg[0], pitch0, (last && gmax_b) ? gmax_b : nullptr, rows_valid,
-                                 !last && A.L[2].prec, xa);
-      __syncthreads();
-      PN_STAMP(3 + 1);
-      lfirst = 2;
-    }
-  }
-  for (int l = lfirst; l < A.num_layers; l++) {
-    const int in = reg[l & 1], pin = (l & 1) ? pitch1 : pitch0;
-    if (A.L[l].fuse_next) {  // layers l and l + 1 together; l + 1 writes region (l + 2) & 1
-      const LayerCtx P = layer_ctx(A, l, b, g_smem + boff[l]), Q = layer_ctx(A, l + 1, b, g_smem + boff[l + 1]);
-      const bool last = l + 2 == A.num_layers;
-      const int out = reg[(l + 2) & 1], pout = ((l + 2) & 1) ? pitch1 : pitch0;
-      float* gm = (last && gmax_b) ? gmax_b : nullptr;
-      // Q is one chunk of its (RB, NB) split: NB = N2 / (16 * column groups)
-      constexpr int kQ = 16 / kWaves > 0 ? 16 / kWaves : 1;
-      const bool op = !last && A.L[l + 2].prec;  // the layer after Q reads bf16 planes
-      if constexpr (kP == 32) {  // two row blocks: each Q split with half the row groups
-        if (Q.N == 256) fused_pair<2, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
-        else fused_pair<1, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op);
-      } else {
-        bool piped = false;
-        if constexpr (kWaves == 16) {
-          if (NDNET_PN_FUSED_PIPE && Q.N == 256 && P.prec && Q.prec && P.KG == 2) {
-            fused_pair_x6p<4, T>(P, Q, in, fbuf, out, pout, gm, rows_valid, op);
-            piped = true;
-          }
-        }
-        if (piped) {
-        } else if (Q.N == 256) fused_pair<4, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
-        else if (Q.N > 64) fused_pair<2, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
-        else fused_pair<1, kQ, T>(P, Q, in, pin, fbuf, out, pout, gm, rows_valid, op, pre);
-      }
-      l++;
-    } else {
-      const LayerCtx C = layer_ctx(A, l, b, g_smem + boff[l]);
-      const bool last = l + 1 == A.num_layers;
-      const int out = reg[(l + 1) & 1], pout = ((l + 1) & 1) ? pitch1 : pitch0;
-      float* gm = (last && gmax_b) ? gmax_b : nullptr;
-      const bool op = !last && A.L[l + 1].prec;  // the next layer reads bf16 planes
-      if constexpr (kP == 32) {
-        // 32-point tiles, 8 waves: two row blocks, columns per wave as the
-        // 64-point form's (one row group, all waves across the columns)
-        if (C.N % 256 == 0) plain_layer<2, 2, T>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 128 == 0) plain_layer<2, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);
-        else plain_layer<1, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);  // N % 64 == 0, or N = 32 (half idle)
-      } else if constexpr (kWaves == 8) {
-        // 8 waves (2 per SIMD, up to 256 registers each): a wave takes up to
-        // four column blocks, so each A fragment feeds NB MFMAs per plane
-        // (tools/ubench/mfma_bf16_peak.hip b9 / b13 vs b3)
-#ifndef NDNET_PN_W8_NB4
-#define NDNET_PN_W8_NB4 1
-#endif
-        if (NDNET_PN_W8_NB4 && C.N % 512 == 0) plain_layer<4, 4, T>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 256 == 0) plain_layer<4, 2, T>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 128 == 0) plain_layer<4, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);
-        else if (C.N % 64 == 0) plain_layer<2, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);
-        else plain_layer<1, 1, T>(C, in, pin, out, pout, gm, rows_valid, op);  // N = 32
-      } else {
-#ifndef NDNET_PN_NB2  // two column blocks per wave on the 1024-wide x6 layers (-5% per layer, r03q)
-#define NDNET_PN_NB2 1
-#endif
-        if (NDNET_PN_NB2 && C.N % 512 == 0 && C.prec) plain_layer<4, 2, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);
-        else if (C.N % 256 == 0) plain_layer<4, 1, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);
-        else if (C.N % 128 == 0) plain_layer<2, 1, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);
-        else plain_layer<1, 1, T>(C, in, pin, out, pout, gm, rows_valid, op, pre);  // N % 64 == 0, or N = 32 (half idle)
-      }
-    }
-#ifdef NDNET_PN_PREFETCH
-    if (l + 1 < A.num_layers) {
-      prefetch_first<T>(A, l + 1, b, pre);
-      layer_barrier();
-    } else {
-      __syncthreads();
-    }
-#else
-    __syncthreads();
-#endif
-    PN_STAMP(3 + l);
-  }
-  if (A.clear && blockIdx.x == 0 && blockIdx.y == 0)
-    for (int64_t i = threadIdx.x; i < A.clear_count; i += kThreads) A.clear[i] = -INFINITY;
-  if (A.mode == 1) {  // log_softmax over channels (ndtnet.py:239), [B][N][C+1] layout
-    const int lg = reg[A.num_layers & 1];
-    const int pl = (A.num_layers & 1) ? pitch1 : pitch0;
-    // 16 lanes per point (a quarter wave): columns q, q + 16, ...; the max
-    // and the sum of exponentials meet in xor shuffles within the group
-    constexpr int kLpr = 16, kRpp = kThreads / kLpr;  // lanes per row, rows per pass
-    const int q = threadIdx.x % kLpr;
-    for (int r0 = 0; r0 < kP; r0 += kRpp) {
-      const int r = r0 + threadIdx.x / kLpr;
-      const int p = p0 + r;
-      const bool live = r < kP && p < A.num_points;  // uniform per 16-lane group
-      const float* row = g_smem + lg + (r < kP ? r : 0) * pl;
-      float m = -INFINITY;
-      for (int c = q; c < A.out_cols; c += kLpr) m = fmaxf(m, row[c]);
-#pragma unroll
-      for (int o = kLpr / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-      float sum = 0.0f;
-      for (int c = q; c < A.out_cols; c += kLpr) sum += expf(row[c] - m);
-#pragma unroll
-      for (int o = kLpr / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-      const float ls = logf(sum);
-      if (live) {
-        float* out = A.out + ((int64_t)b * A.num_points + p) * A.out_cols;
-        for (int c = q; c < A.out_cols; c += kLpr) out[c] = (row[c] - m) - ls;
-      }
-    }
-  }
-  PN_STAMP(15);
+  static_assert(T != 2, "the fp16 form is k_pn_chain_f16");
+  constexpr const ndnet_pn_f16* X = nullptr;
+  constexpr int flag_base = 0;
+#define PN_BODY_FAIL return
+#include "pointnet_chain_body.inc"
+#undef PN_BODY_FAIL
+}
+
+// The fp16 form with its fallback: a tile whose activations leave fp16's window (pn_chain_body<2> returns
+// false, the whole workgroup at one point, nothing of the tile stored yet) runs k_pn_chain<6>'s body from
+// the start, on the same LDS layout -- the fp16 planes are the first two of the three bf16 ones -- and is
+// counted.
+__global__ void __launch_bounds__(kThreads) k_pn_chain_f16(ndnet_pn_chain A, ndnet_pn_f16 X, int planes, int fbuf,
+                                                           int bias_base, int flag_base) {
+  if (pn_chain_body<2>(A, &X, planes, fbuf, bias_base, flag_base)) return;
+  __syncthreads();  // every wave has left the fp16 body: its LDS is free
+  if (threadIdx.x == 0) atomicAdd(X.fallbacks, 1u);
+  pn_chain_body<6>(A, nullptr, planes, fbuf, bias_base, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -2022,7 +1763,8 @@ __device__ inline uint16_t fold_bf16(float x) {  // torch's float -> bfloat16: r
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
-__device__ inline float fold_w(const ndnet_pn_fold_job& J, int n, int k) {
+template <class Job>
+__device__ inline float fold_w(const Job& J, int n, int k) {
 #pragma clang fp contract(off)
   if (n >= J.N || k >= J.K) return 0.0f;
   const float w = J.w[(int64_t)n * J.ld + J.k0 + k];
@@ -2132,6 +1874,67 @@ __global__ void __launch_bounds__(kFoldThreads) k_pn_fold(const ndnet_pn_fold_jo
       static_cast<float*>(J.out)[u] = v;
     }
   }
+}
+
+// ---- the fp16 planes of a split layer (ndnet_pn_fold16_run, include/ndnet_pointnet.h) ----
+// Launch 1: the maximum of |fw| over part blockIdx.x of kFold16Parts interleaved parts of job blockIdx.y's
+// layer (fmaxf: a NaN weight takes no part), one float each -- no atomics, so nothing to zero between folds.
+constexpr int kFold16Parts = 16;
+
+__global__ void __launch_bounds__(kFoldThreads) k_pn_fold16_max(const ndnet_pn_fold16_job* __restrict__ jobs) {
+#pragma clang fp contract(off)
+  __shared__ float s_m[kFoldThreads];
+  const ndnet_pn_fold16_job J = jobs[blockIdx.y];
+  const int64_t total = (int64_t)J.N * J.K;
+  float m = 0.0f;
+  for (int64_t e = (int64_t)blockIdx.x * kFoldThreads + threadIdx.x; e < total; e += (int64_t)kFold16Parts * kFoldThreads)
+    m = fmaxf(m, fabsf(fold_w(J, (int)(e / J.K), (int)(e % J.K))));
+  s_m[threadIdx.x] = m;
+  __syncthreads();
+  for (int o = kFoldThreads / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_m[threadIdx.x] = fmaxf(s_m[threadIdx.x], s_m[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) J.partial[blockIdx.x] = s_m[0];
+}
+
+// The layer's exponent s from its maximum: max 2^s in [2^13, 2^14); 0 for a zero or non-finite maximum.  Any
+// finite maximum has s >= -114, which 2^s and 2^-s both hold; s stops at 100 (a maximum below 2^-87 then
+// lands under 2^13: fewer bits of weights that small, never an overflow).
+__device__ inline int fold16_exp(float m) {
+  if (!(m > 0.0f) || !(m < INFINITY)) return 0;
+  const int s = 13 - ilogbf(m);
+  return s > 100 ? 100 : s;
+}
+
+// Launch 2: one thread per 8 consecutive k of one column -- 16 bytes of each plane, as NDNET_FOLD_FRAG6's
+// units, [cb][kg][plane][kq][cl][j] with two planes; the job's first thread stores 2^-s.
+__global__ void __launch_bounds__(kFoldThreads) k_pn_fold16_frag(const ndnet_pn_fold16_job* __restrict__ jobs) {
+#pragma clang fp contract(off)
+  const ndnet_pn_fold16_job J = jobs[blockIdx.y];
+  const int64_t u = (int64_t)blockIdx.x * kFoldThreads + threadIdx.x;
+  if (u >= (int64_t)J.Kp * J.Np / 8) return;
+  float m = 0.0f;
+#pragma unroll
+  for (int i = 0; i < kFold16Parts; i++) m = fmaxf(m, J.partial[i]);
+  const int s = fold16_exp(m);
+  const float up = ldexpf(1.0f, s);
+  if (u == 0) *J.scale = ldexpf(1.0f, -s);
+  const int kgs = J.Kp / 32;
+  const int cl = (int)(u % 16), kq = (int)(u / 16 % 4), kg = (int)(u / 64 % kgs), cb = (int)(u / (64 * kgs));
+  const int k = 32 * kg + 8 * kq, n = 16 * cb + cl;
+  f16x8 h8, l8;
+#pragma unroll
+  for (int t = 0; t < 8; t++) {
+    const float x = fold_w(J, n, k + t) * up;  // exact but for an underflow far below the layer's maximum
+    const _Float16 h = (_Float16)x;            // round to nearest even, as the activations' split
+    h8[t] = h;
+    l8[t] = (_Float16)(x - (float)h);
+  }
+  const int64_t unit = u % 64 + (u / 64) * 128;  // 64 units per (cb, kg), two planes of them
+  f16x8* o = reinterpret_cast<f16x8*>(J.out);
+  o[unit] = h8;
+  o[unit + 64] = l8;
 }
 #endif
 
@@ -2303,6 +2106,32 @@ int ndnet_pn_fold_run(const ndnet_pn_fold_job* jobs, int num_jobs, int64_t num_b
   return hipGetLastError() == hipSuccess ? 0 : -21;
 }
 
+int ndnet_pn_fold16_check(const ndnet_pn_fold16_job* jobs, int num_jobs, int64_t* max_units) {
+  if (!jobs || num_jobs <= 0 || num_jobs > 65535 || !max_units) return -20;
+  int64_t mu = 0;
+  for (int i = 0; i < num_jobs; i++) {
+    const ndnet_pn_fold16_job& J = jobs[i];
+    if (!J.w || !J.out || !J.partial || !J.scale || (uintptr_t)J.out % 16 || J.N <= 0 || J.K <= 0 || J.k0 < 0 ||
+        J.ld < J.k0 + J.K || J.Kp < J.K || J.Np < J.N || J.Kp % 32 || J.Np % 16 || (J.gamma == nullptr) != (J.var == nullptr) ||
+        (J.gamma && !(J.eps >= 0.0f)))
+      return -20;
+    const int64_t units = (int64_t)J.Kp * J.Np / 8;
+    if (units > mu) mu = units;
+  }
+  if ((mu + kFoldThreads - 1) / kFoldThreads > 0x7fffffff) return -20;
+  *max_units = mu;
+  return 0;
+}
+
+int ndnet_pn_fold16_run(const ndnet_pn_fold16_job* jobs, int num_jobs, int64_t max_units, void* stream) {
+  const int64_t blocks = (max_units + kFoldThreads - 1) / kFoldThreads;
+  if (!jobs || num_jobs <= 0 || num_jobs > 65535 || max_units <= 0 || blocks > 0x7fffffff) return -20;
+  k_pn_fold16_max<<<dim3(kFold16Parts, num_jobs), kFoldThreads, 0, (hipStream_t)stream>>>(jobs);
+  // the planes, scaled by what the first launch has just found, behind it in stream order
+  k_pn_fold16_frag<<<dim3((unsigned)blocks, num_jobs), kFoldThreads, 0, (hipStream_t)stream>>>(jobs);
+  return hipGetLastError() == hipSuccess ? 0 : -21;
+}
+
 // One fused point-MLP chain over `batch` clouds on `stream` (see pointnet.h).
 
 // Timing builds: zeroes the stamp array (before a launch whose stamps are read)
@@ -2337,11 +2166,12 @@ int ndnet_pn_debug_stamps(unsigned long long* host, int wgs) {
     return -20;                                                                                \
   } while (0)
 
-#if NDNET_PN_TILE == 64
-int ndnet_pn_chain_run(const ndnet_pn_chain* args, int batch, void* stream) {
-#else
-int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) {
-#endif
+}  // extern "C"
+
+namespace {
+
+// ext: the fp16 form's block (ndnet_pn_chain_f16_run), or NULL
+int chain_launch(const ndnet_pn_chain* args, const ndnet_pn_f16* ext, int batch, void* stream) {
   if (!args || batch <= 0 || args->num_layers < 1 || args->num_layers > NDNET_PN_MAX_LAYERS || args->num_points <= 0 ||
       args->in_cols < 1 || args->in_cols > args->L[0].K || args->in_cols > args->x_ld)
     PN_ARG_FAIL();
@@ -2439,19 +2269,41 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
     nbias += args->L[l].N;
   }
   total = (size_t)bias_base + nbias;
+  int flag_base = 0;
+  if (ext) {
+    // the fp16 form: prec 1 layers only (its fallback is k_pn_chain<6>'s body), each with its planes and
+    // scale; a pooled last layer fed by a fused one would max-pool before its input's window is known
+    if (smode != 1 || !ext->fallbacks) PN_ARG_FAIL();
+    for (int l = 0; l < args->num_layers; l++) {
+      if (!args->L[l].prec) continue;
+      if (!ext->w16[l] || !ext->scale[l] || (uintptr_t)ext->w16[l] % 16 || args->L[l].w_cloud_stride) PN_ARG_FAIL();
+      // a split layer produced in chunks into the next (the layered seg head's 64 -> 512) has no caller in
+      // this form -- the forward takes it only with chain D collapsed, whose fused P is fp32 -- and no test
+      if (args->L[l].fuse_next) PN_ARG_FAIL();
+    }
+    const int nl = args->num_layers;
+    if (args->mode == 0 && nl >= 2 && args->L[nl - 2].fuse_next) PN_ARG_FAIL();
+    flag_base = (int)total;  // the window words, one per layer, behind the biases
+    total += NDNET_PN_MAX_LAYERS;
+  }
   const size_t lds = sizeof(float) * total;
-  const int ki = smode > 1 ? smode - 1 : 0;  // k_pn_chain<6>, <3>, <1>
-  auto* const kernel = ki == 0 ? k_pn_chain<6> : ki == 1 ? k_pn_chain<3> : k_pn_chain<1>;
-  static bool attr_set[3] = {false, false, false};
+  const int ki = ext ? 3 : smode > 1 ? smode - 1 : 0;  // k_pn_chain<6>, <3>, <1>, k_pn_chain_f16
+  const void* const kernel = ki == 0   ? (const void*)k_pn_chain<6>
+                             : ki == 1 ? (const void*)k_pn_chain<3>
+                             : ki == 2 ? (const void*)k_pn_chain<1>
+                                       : (const void*)k_pn_chain_f16;
+  static bool attr_set[4] = {false, false, false, false};
   if (!attr_set[ki]) {
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-        hipSuccess)
-      return -21;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -21;
     attr_set[ki] = true;
   }
   if (lds > 160 * 1024) PN_ARG_FAIL();
   dim3 grid((args->num_points + kP - 1) / kP, batch);
-  kernel<<<grid, kThreads, lds, (hipStream_t)stream>>>(*args, planes, fbuf_off, bias_base);
+  hipStream_t st = (hipStream_t)stream;
+  if (ki == 0) k_pn_chain<6><<<grid, kThreads, lds, st>>>(*args, planes, fbuf_off, bias_base);
+  else if (ki == 1) k_pn_chain<3><<<grid, kThreads, lds, st>>>(*args, planes, fbuf_off, bias_base);
+  else if (ki == 2) k_pn_chain<1><<<grid, kThreads, lds, st>>>(*args, planes, fbuf_off, bias_base);
+  else k_pn_chain_f16<<<grid, kThreads, lds, st>>>(*args, *ext, planes, fbuf_off, bias_base, flag_base);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     fprintf(stderr, "ndnet_amd: k_pn_chain launch failed: %s\n", hipGetErrorString(e));
@@ -2459,5 +2311,39 @@ int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) 
   }
   return 0;
 }
+
+}  // namespace
+
+extern "C" {
+
+#if NDNET_PN_TILE == 64
+int ndnet_pn_chain_run(const ndnet_pn_chain* args, int batch, void* stream) {
+  return chain_launch(args, nullptr, batch, stream);
+}
+
+int ndnet_pn_chain_f16_run(const ndnet_pn_chain* args, const ndnet_pn_f16* ext, int batch, void* stream) {
+  if (!ext) PN_ARG_FAIL();
+  return chain_launch(args, ext, batch, stream);
+}
+
+int ndnet_pn_take_f16_fallbacks(uint32_t* device_counter, void* stream) {
+  if (!device_counter) return -20;
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t v = 0;
+  if (hipMemcpyAsync(&v, device_counter, sizeof v, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemsetAsync(device_counter, 0, sizeof v, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return -21;
+  return v > 0x7fffffffu ? 0x7fffffff : (int)v;
+}
+#else
+int ndnet_pn_chain_run_t32(const ndnet_pn_chain* args, int batch, void* stream) {
+  return chain_launch(args, nullptr, batch, stream);
+}
+
+int ndnet_pn_chain_f16_run_t32(const ndnet_pn_chain* args, const ndnet_pn_f16* ext, int batch, void* stream) {
+  if (!ext) PN_ARG_FAIL();
+  return chain_launch(args, ext, batch, stream);
+}
+#endif
 
 }  // extern "C"

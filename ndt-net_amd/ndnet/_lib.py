@@ -187,6 +187,12 @@ POINTNET_EXPORTS: dict = {
     "ndnet_pn_pool12_tail_run": (_I, [_P, _I, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _I, _P, _I, _I, _P]),
     "ndnet_pn_fold_prepare": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64)]),
     "ndnet_pn_fold_run": (_I, [_P, _I, ctypes.c_int64, _P]),
+    # the fp16 two-slice form of the chains' split layers
+    "ndnet_pn_chain_f16_run": (_I, [_P, _P, _I, _P]),
+    "ndnet_pn_chain_f16_run_t32": (_I, [_P, _P, _I, _P]),
+    "ndnet_pn_take_f16_fallbacks": (_I, [_P, _P]),
+    "ndnet_pn_fold16_check": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "ndnet_pn_fold16_run": (_I, [_P, _I, ctypes.c_int64, _P]),
 }
 
 

@@ -25,6 +25,11 @@ relu(x (W1f[b] M) + (b1 M + bM)), composed in its prologue, and D opens with a
 per-cloud 12 -> 512 layer (``ndnet_pn_fold_seg_run`` writes its weights,
 ``ndnet_pn_fc_mfma_bias_run`` its bias rows) fused into 512 -> 256.
 
+In that default forward (the composed tail, B and D collapsed) the split layers of chains A, B and
+D run on two fp16 slices and three products instead of three bf16 slices and six (``SLICES``,
+``ndnet_pn_chain_f16_run``): the same accuracy class on half the matrix instructions, each tile
+falling back to the bf16 code inside the launch when its activations leave fp16's window.
+
 Every BatchNorm (running statistics) is folded into the preceding 1x1 conv /
 linear layer.  The per-point GEMMs run on the matrix cores: eleven layers
 (the three 128 -> 1024 / F max-pooled convs, the t2-folded conv2, the seg
@@ -55,6 +60,7 @@ publishes the result for chain D.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import torch
@@ -172,6 +178,19 @@ class _Chain(ctypes.Structure):
                 ("x_nonfinite_nan", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
 
 
+class _F16(ctypes.Structure):  # ndnet_pn_f16: what the fp16 two-slice form adds to a chain's argument block
+    _fields_ = [("w16", ctypes.c_void_p * MAX_LAYERS), ("scale", ctypes.c_void_p * MAX_LAYERS),
+                ("fallbacks", ctypes.c_void_p)]
+
+
+class _Fold16Job(ctypes.Structure):  # ndnet_pn_fold16_job
+    _fields_ = [("w", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("var", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("partial", ctypes.c_void_p), ("scale", ctypes.c_void_p),
+                ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("ld", ctypes.c_int32), ("k0", ctypes.c_int32),
+                ("Kp", ctypes.c_int32), ("Np", ctypes.c_int32), ("eps", ctypes.c_float),
+                ("reserved", ctypes.c_int32)]
+
+
 class _FoldJob(ctypes.Structure):  # ndnet_pn_fold_job (include/ndnet_pointnet.h)
     _fields_ = [("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
                 ("beta", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p),
@@ -238,6 +257,34 @@ def _frag_x6(wT: torch.Tensor) -> torch.Tensor:
     planes = torch.stack([h, m, lo])                                  # [3, K, N]
     v = planes.reshape(3, K // 32, 4, 8, N // 16, 16)                 # plane, kg, kq, j, cb, cl
     return v.permute(4, 1, 0, 2, 5, 3).reshape(-1).contiguous()        # cb, kg, plane, kq, cl, j
+
+
+def _f16_exponent(wmax: float) -> int:
+    """The layer-wide exponent s of the fp16 form: max |w| 2^s in [2^13, 2^14), at most 100 (a
+    maximum below 2^-87 stays under 2^13; every finite one lands below 2^14: s >= -114, which fp32
+    holds); 0 for a maximum that is zero or not finite (ndnet_pn_fold16_run's rule)."""
+    if not (wmax > 0.0) or not math.isfinite(wmax):
+        return 0
+    return min(100, 13 - (math.frexp(wmax)[1] - 1))
+
+
+def _frag_f16(wT: torch.Tensor):
+    """Plain W^T [K, N] (K % 32 == 0, N % 16 == 0) -> (planes, scale): the two fp16 planes of
+    ndnet_pn_f16.w16, flattened, and the one float 2^-s the kernel reads with them.  W^T 2^s = h + l with
+    h = fp16(w 2^s), l = fp16(w 2^s - h), both to nearest even (the power of two scales exactly),
+    [cb][kg][plane][kq][cl][j] with k = 32 kg + 8 kq + j, n = 16 cb + cl: the layout of ``_frag_x6`` with
+    two planes per k-group.  Bit for bit what ndnet_pn_fold16_run writes."""
+    K, N = wT.shape
+    w = wT.float()
+    # the device maximum is an fmaxf chain: a NaN weight takes no part in it
+    s = _f16_exponent(float(w.abs().nan_to_num(nan=0.0, posinf=float("inf")).max()) if w.numel() else 0.0)
+    x = w * (2.0 ** s)
+    h = x.to(torch.float16)
+    lo = (x - h.float()).to(torch.float16)
+    planes = torch.stack([h, lo])                                      # [2, K, N]
+    v = planes.reshape(2, K // 32, 4, 8, N // 16, 16)                  # plane, kg, kq, j, cb, cl
+    scale = torch.full((1,), 2.0 ** -s, dtype=torch.float32, device=wT.device)
+    return v.permute(4, 1, 0, 2, 5, 3).reshape(-1).contiguous(), scale  # cb, kg, plane, kq, cl, j
 
 
 def _prod64(a: torch.Tensor, rhs: torch.Tensor, bias=None) -> torch.Tensor:
@@ -347,6 +394,11 @@ class _Folded:
                     self.wide.append(self.D_tail[2][0])
             self.frag = {id(w): _frag(w) for w in self.chain_w}
             self.frag6 = {id(w): _frag_x6(w) for w in self.wide}
+            # ... and as two fp16 planes with a layer-wide scale, built by ``ensure_f16`` when a forward
+            # first takes the fp16 form (``SLICES``; ``_Workspace.uses_f16``): nothing of it exists, and no
+            # re-fold pays for it, under NDNET_PN_SLICES=bf16 or where the form never runs
+            self.frag16, self.scale16, self.part16 = {}, {}, {}
+            self._recipes16 = []  # (w, layer, bn, k0, K) of every split layer (``_fold_jobs``)
             # a layer whose K is a model width (the seg head's global-feature bias, the
             # classification head's conv1: K = F) has it padded to a multiple of 16 with
             # zero rows: the layer then reads g3's padded columns, which chain C leaves at 0
@@ -361,8 +413,10 @@ class _Folded:
         # copy.  The mode itself ("x6" / "x3" / "bf16" / "fp32") does not enter: every mode
         # reads these tensors (frag6 or frag), and the argument blocks are kept per mode
         self.prec = (X6_NARROW,)
+        self.jobs16 = []  # the fp16 planes' recipes (ndnet_pn_fold16_job), a list of their own beside ``products``
         self.jobs = self._fold_jobs(m)
         self._dev_jobs, self._blocks = None, 0
+        self._dev_jobs16, self._units16 = None, 0
 
     def _fold_seg(self, m, conv) -> None:
         """The segmentation head (chain D and its global-feature bias)."""
@@ -475,6 +529,7 @@ class _Folded:
         for w in self.wide:
             layer, bn, k0, K = src[id(w)]
             add(2, self.frag6[id(w)], layer, bn, k0, K, *w.shape)
+            self._recipes16.append((w, layer, bn, k0, K))
         for w in self.fcs:
             layer, bn, k0, K = src[id(w)]
             add(1, self.fcf[id(w)], layer, bn, k0, K, _pad(w.shape[1], 16), w.shape[0])
@@ -482,6 +537,22 @@ class _Folded:
             add(1, self.h3f, m.conv3, None, 0, 256, 256, self.Cp)
             bias(self.h3b, m.conv3, None)
         return jobs
+
+    def ensure_f16(self) -> bool:
+        """The fp16 planes, scales and fold scratch of every split layer, built from the folded weights as
+        they are now, with their recipes in ``jobs16`` (a list of their own beside ``products``: every
+        later in-place re-fold re-runs them on the device).  Never for the baseline, whose chains stay
+        layered.  -> whether the planes exist."""
+        if self.frag16 or self.baseline:
+            return bool(self.frag16)
+        with torch.no_grad():
+            for w in self.wide:
+                self.frag16[id(w)], self.scale16[id(w)] = _frag_f16(w)
+                self.part16[id(w)] = torch.zeros(16, dtype=torch.float32, device=w.device)  # the fold's scratch
+        self.jobs16 = [(self.frag16[id(w)], self.part16[id(w)], self.scale16[id(w)], layer, bn, k0, K, *w.shape)
+                       for w, layer, bn, k0, K in self._recipes16]
+        self._dev_jobs16 = None
+        return True
 
     def can_refold(self, tensors) -> bool:
         """In place: the same parameter / buffer tensors, on a GPU, with the same set of
@@ -525,6 +596,23 @@ class _Folded:
         rc = _lib.lib().ndnet_pn_fold_run(self._dev_jobs.data_ptr(), len(self.jobs) + len(self.products),
                                           self._blocks, _lib.stream_ptr(dev))
         _lib.check(rc, "ndnet_pn_fold_run")
+        if not self.jobs16:
+            return
+        # the fp16 planes and their scales from the live weights: two more launches, no host read
+        if self._dev_jobs16 is None:
+            arr = (_Fold16Job * len(self.jobs16))()
+            for J, (out, part, scale, layer, bn, k0, K, Kp, Np) in zip(arr, self.jobs16):
+                J.w, J.out, J.partial, J.scale = layer.weight.data_ptr(), out.data_ptr(), part.data_ptr(), scale.data_ptr()
+                J.N, J.K, J.ld, J.k0, J.Kp, J.Np = layer.weight.shape[0], K, layer.weight.shape[1], k0, Kp, Np
+                if bn is not None:
+                    J.gamma, J.var, J.eps = bn.weight.data_ptr(), bn.running_var.data_ptr(), bn.eps
+            units = ctypes.c_int64()
+            _lib.check(_lib.lib().ndnet_pn_fold16_check(arr, len(arr), ctypes.byref(units)), "ndnet_pn_fold16_check")
+            self._dev_jobs16 = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+            self._units16 = units.value
+        rc = _lib.lib().ndnet_pn_fold16_run(self._dev_jobs16.data_ptr(), len(self.jobs16), self._units16,
+                                            _lib.stream_ptr(dev))
+        _lib.check(rc, "ndnet_pn_fold16_run")
 
 
 def _tensors(m) -> list:
@@ -637,6 +725,12 @@ def _run_chain(ch, x: torch.Tensor, out=None) -> None:
     assert x.stride(1) == ch.x_ld and x.stride(2) == 1 and x.dtype == torch.float32
     ch.x = x.data_ptr()
     ch.out = out.data_ptr() if out is not None else None
+    ext = getattr(ch, "f16", None)  # the fp16 two-slice form (``_Workspace.uses_f16``): the block beside the chain's
+    if ext is not None:
+        name = "ndnet_pn_chain_f16_run_t32" if _use_t32(x.shape[0], x.shape[1], x.device) else "ndnet_pn_chain_f16_run"
+        rc = getattr(_lib.lib(), name)(ctypes.byref(ch), ctypes.byref(ext), x.shape[0], _lib.stream_ptr(x.device))
+        _lib.check(rc, name)
+        return
     if _use_t32(x.shape[0], x.shape[1], x.device):
         rc = _lib.lib().ndnet_pn_chain_run_t32(ctypes.byref(ch), x.shape[0], _lib.stream_ptr(x.device))
         _lib.check(rc, "ndnet_pn_chain_run_t32")
@@ -723,6 +817,7 @@ class _Workspace:
             self._specs[(True, True)] = both
         self.N = N
         self.structs = {}
+        self.f16_fallbacks = None  # device counter of the fp16 form's fallback tiles (``take_f16_fallbacks``)
         self.pool12 = None  # chain C's 12 -> F argument block (``uses_pool12``), built at its first launch
         self._pool12 = {}   # ... per form: from the composed tail (``FOLD_PRODUCTS``) or from the layers
 
@@ -769,6 +864,26 @@ class _Workspace:
         and bit for bit."""
         return bool(FOLD_PRODUCTS) and bool(COLLAPSE) and self.uses_pool12()
 
+    def uses_f16(self) -> bool:
+        """Whether the chains' split layers run in the fp16 two-slice form (``SLICES``): only in the "x6"
+        mode's default forward -- the composed tail, chain B collapsed and, for a segmentation model,
+        chain D collapsed.  With any of NDNET_PN_COLLAPSE=0, NDNET_PN_FOLD_PRODUCTS=0,
+        NDNET_PN_BACKBONE=chain, NDNET_PN_FOLD_T2=chain, a many-classes model, the baseline or a reduced
+        mode, the forward is the bf16 three-slice one, launch for launch and bit for bit."""
+        return (SLICES == "f16" and self.mode == "x6" and self.uses_tail() and self.collapses_b()
+                and (not self.W.seg or self.collapses_d()) and self.W.ensure_f16())
+
+    def take_f16_fallbacks(self) -> int:
+        """Tiles that left fp16's window and ran the bf16 form since the last call (it waits for the
+        current stream; 0 when no forward of this workspace ran the fp16 form)."""
+        if self.f16_fallbacks is None:
+            return 0
+        rc = _lib.lib().ndnet_pn_take_f16_fallbacks(self.f16_fallbacks.data_ptr(),
+                                                    _lib.stream_ptr(self.f16_fallbacks.device))
+        if rc < 0:
+            _lib.check(rc, "ndnet_pn_take_f16_fallbacks")
+        return rc
+
     def hip_layers(self, mode: str) -> list:
         """The chains' layers (A-D; A-C for a classification model) for ``_build_chain`` in one precision mode:
         every layer with a split-bf16 copy takes the mode's prec (all modes
@@ -778,7 +893,7 @@ class _Workspace:
         def shared(wb):
             w, b = wb
             if mode != "fp32" and id(w) in W.frag6:
-                return (W.frag6[id(w)], 0, b, w.shape[0], w.shape[1], MODES[mode])
+                return (W.frag6[id(w)], 0, b, w.shape[0], w.shape[1], MODES[mode], w)  # w: the layer, for ``uses_f16``
             return (W.frag[id(w)], 0, b, w.shape[0], w.shape[1])
 
         # conv1: per cloud with t1 folded in; the baseline's is the shared layer (t1 went into the points)
@@ -811,13 +926,32 @@ class _Workspace:
         W = self.W
         collapse_b, collapse_d = self.collapses_b(), self.collapses_d()
         # argument blocks per mode and form
+        f16 = self.uses_f16()
         skey = self.mode if not collapse_b else (self.mode, "collapse B+D" if collapse_d else "collapse B")
+        if f16:
+            skey = skey + ("f16",)
         structs = self.structs.get(skey)
         if structs is None:
             # input rows: [B,N,12] blocks; the baseline's chain A reads the points themselves, B-D ws.xt
             x_lds = (3, 4, 4, 4) if W.baseline else (12, 12, 12, 12)
+            hls = self.hip_layers(self.mode)
             structs = self.structs[skey] = [_build_chain(self.N, s[0], hl, s[2], s[3], x_ld=xl, **s[4])
-                                            for s, hl, xl in zip(self.specs, self.hip_layers(self.mode), x_lds)]
+                                            for s, hl, xl in zip(self.specs, hls, x_lds)]
+            if f16:
+                # every chain with split layers (chain C is the 12 -> F launch here) takes the fp16 block
+                # beside its own: the planes and scale of each split layer, and this workspace's counter
+                if self.f16_fallbacks is None:
+                    self.f16_fallbacks = torch.zeros(1, dtype=torch.int32, device=self.gbuf.device)
+                for blk, hl in zip(structs, hls):
+                    if not any(len(t) == 7 for t in hl):
+                        continue
+                    ext = _F16()
+                    for l, t in enumerate(hl):
+                        if len(t) == 7:
+                            ext.w16[l] = W.frag16[id(t[6])].data_ptr()
+                            ext.scale[l] = W.scale16[id(t[6])].data_ptr()
+                    ext.fallbacks = self.f16_fallbacks.data_ptr()
+                    blk.f16 = ext
             if W.seg:  # the last chain re-arms the max-pool buffer (-inf) for the next forward
                 structs[3].clear = self.gbuf.data_ptr()
                 structs[3].clear_count = self.gbuf.numel()
@@ -907,6 +1041,18 @@ COLLAPSE = os.environ.get("NDNET_PN_COLLAPSE", "1") == "1"
 # keeps ndnet_pn_pool12_run, bit for bit.  A module attribute read when a forward picks its argument
 # blocks, like BACKBONE.
 FOLD_PRODUCTS = os.environ.get("NDNET_PN_FOLD_PRODUCTS", "1") == "1"
+# The slices of the x6 mode's split layers: "f16" (default) runs them as two fp16 slices and three products
+# per operand pair (ndnet_pn_chain_f16_run: half of x6's matrix instructions in the same accuracy class),
+# each tile falling back to the bf16 three-slice code when its activations leave fp16's window, wherever
+# ``_Workspace.uses_f16`` allows; "bf16" keeps ndnet_pn_chain_run everywhere, bit for bit.  A module
+# attribute read when a forward picks its argument blocks, like BACKBONE.
+def _slices(value: str) -> str:
+    if value not in ("f16", "bf16"):
+        raise ValueError(f"NDNET_PN_SLICES must be 'f16' or 'bf16', not {value!r}")
+    return value
+
+
+SLICES = _slices(os.environ.get("NDNET_PN_SLICES", "f16"))
 # TNet(3)'s tail (fc3 + the t1 fold of conv1): "chain" (default) computes it in
 # chain B's prologue, per workgroup (ndnet_pn_chain.head_*: one launch and one
 # boundary fewer); "kernel" runs ndnet_pn_head3_run before chain B
