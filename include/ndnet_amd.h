@@ -377,6 +377,49 @@ int ndnet_ndt_debug_wq_marks(void *plan, unsigned long long *marks, uint32_t *it
 int ndnet_debug_lu_chain(const double *d_A, uint32_t n, int steps, double *d_states, uint32_t *d_ps,
                          uint32_t *d_flags, void *stream);
 
+/* The per-function entries below run one device function of the NDT
+ * arithmetic (csrc/ndt_device.h, csrc/ndt_log.h) per element, compiled in the
+ * stage kernels' translation unit with their flags: element i by thread i of
+ * the grid, in 256-thread workgroups.  For the parity tests; each is
+ * stream-ordered on `stream`. */
+
+/* d_y[i] = the portable natural logarithm (ndnet_log, the KL score's log) of
+ * d_x[i], n doubles. */
+int ndnet_debug_log(const double *d_x, uint32_t n, double *d_y, void *stream);
+
+/* One KL event per pair of row-major 3x3 matrices d_P [n][9], d_Q [n][9]:
+ * the device LU decomposition of a copy of each, then what the KL stage does
+ * from two chain states (kullback_leibler.c:57-115 for counts above 1):
+ * d_flag [n] = both determinants and sign determinants non-zero; where it is
+ * 1, d_inv [n][9] = the inverse of Q from its LU (the GSL 2.7.1 LU_invert
+ * restatement) and d_score [n] = the divergence; where it is 0 both are 0. */
+int ndnet_debug_kl_pairs(const double *d_P, const double *d_Q, uint32_t n, double *d_score, uint32_t *d_flag,
+                         double *d_inv, void *stream);
+
+/* Voxel keys of n double points d_pts64 [n][3] in the grid of offset off[3],
+ * cells len[3] (host arrays) and voxel size vs (voxel.c:83-103 + 177-189):
+ * d_key64 [n] = the double-precision key (0xffffffff out of grid) and
+ * d_key32 [n] = the single-precision screen's key of the point cast to
+ * float, 0xfffffffe where the screen leaves the point to the double path.
+ * Preconditions, those of the screen's callers: every off[a] is exactly a
+ * float (else NDNET_ERR_ARG), and d_key32[i] means something only for a point
+ * that is a float and has no coordinate below off. */
+int ndnet_debug_voxel_keys(const double *d_pts64, uint32_t n, const double *off, const uint32_t *len, double vs,
+                           uint32_t *d_key64, uint32_t *d_key32, void *stream);
+
+/* d_q[i] = d_t[i] / d_n[i] as the one-ND-per-lane Welford fold divides: three
+ * multiply-adds on the refined hardware reciprocal of the count.  d_n[i] >= 1;
+ * bit-equal to the IEEE division for 2^-969 < |t| < 2^900, and a zero t gives
+ * +0 whatever its sign. */
+int ndnet_debug_div_recip(const double *d_t, const uint32_t *d_n, uint32_t count, double *d_q, void *stream);
+
+/* The order-preserving 64-bit keys of n doubles (no NaN): d_key[i] = the
+ * ascending key of d_x[i] (-0.0 below +0.0), d_back[i] = the double that key
+ * maps back to, d_score_key[i] = the KL list's key (ascending key =
+ * descending score, -0.0 keyed as +0.0). */
+int ndnet_debug_ord_keys(const double *d_x, uint32_t n, unsigned long long *d_key, double *d_back,
+                         unsigned long long *d_score_key, void *stream);
+
 /* Library identification (no GPU needed). */
 const char *ndnet_amd_version(void);
 

@@ -94,15 +94,8 @@ NDNET_FN uint32_t voxel_key(double x, double y, double z, const double* off, con
 // Q = (p - off) / vs, and the reference's fl64(fl64(p - off) / vs) within
 // 2^-52 |Q|; so where frac(q) is more than |q| 2^-19 away from 0 and 1, both
 // floor to the same integer.  Otherwise (including q = 0 and NaN) the caller
-// takes voxel_key.  (axis_index_f32 is the per-axis form, kept for tests.)
-NDNET_FN uint32_t axis_index_f32(float p, float off32, float inv32, bool& ok) {
-  const float q = (p - off32) * inv32;
-  const float f = floorf(q);
-  const float r = q - f;
-  const float tol = q * 0x1p-19f;
-  ok = r > tol && r < 1.0f - tol && q < 8388608.0f;
-  return (uint32_t)(int32_t)(ok ? f : 0.0f);
-}
+// takes voxel_key.  voxel_key_f32 below is the three-axis form with one
+// tolerance for the whole grid.
 
 constexpr uint32_t kKeyRedo = 0xfffffffeu;  // voxel_key_f32: take voxel_key for this point
 
@@ -134,8 +127,7 @@ NDNET_FN uint32_t voxel_key_f32(float x, float y, float z, const float* off32, f
 // 2^-900 < |x| < 2^900 none of that applies, so the result is exactly
 // fma(x - n q0, r, q0) with r = recip_refined(n): bit-identical to x / n, and
 // r (depending on n only) is computed once per sample instead of once per
-// division.  Zero is returned as is (0 / n keeps the sign of the zero).
-// Callers take x / n when *ok is false.
+// division.
 NDNET_FN double recip_refined(double n) {
   double r = __builtin_amdgcn_rcp(n);
   double e = fma(-n, r, 1.0);
@@ -144,58 +136,19 @@ NDNET_FN double recip_refined(double n) {
   r = fma(r, e, r);
   return r;
 }
-NDNET_FN double div_by_recip(double x, double n, double r, bool& ok) {
-  const double ax = fabs(x);
-  ok = (ax > 0x1p-900 && ax < 0x1p900) || x == 0.0;
-  const double q0 = x * r;
-  const double rem = fma(-n, q0, x);
-  // x / n has the sign of x (n > 0); for x = -0 the fma sequence gives +0
-  return copysign(fma(rem, r, q0), x);
-}
 
-// div_by_recip without the operand checks, for callers that have bounded the
-// operands (2^-969 < |x| < 2^900 or x == 0) beforehand.  A zero x gives +0:
-// only its sign could differ from x / n, and the Welford sums it feeds start
-// at +0 and can never become -0, so no sum changes.
+// The three-step division t / n of the light Welford fold, stated once: the
+// fold (k_welford_q's one-ND-per-lane form, ndt_kernels.hip) writes the same
+// three operations out by hand, interleaved with its other chains, for
+// operands it has bounded beforehand (2^-969 < |x| < 2^900 or x == 0).  A
+// zero x gives +0: only its sign could differ from x / n, and the Welford
+// sums it feeds start at +0 and can never become -0, so no sum changes.
+// ndnet_debug_div_recip runs this function against the IEEE division
+// (tests/test_ndt_device_gpu.py).
 NDNET_FN double div_fast(double x, double n, double r) {
   const double q0 = x * r;
   const double rem = fma(-n, q0, x);
   return fma(rem, r, q0);
-}
-
-// Welford state of one voxel (normal_distributions.h:41-51, class handled apart).
-struct Welford {
-  double mean[3];
-  double m2[3];
-  double cov[9];
-  uint64_t n;
-};
-
-NDNET_FN void welford_init(Welford& w) {
-  for (int j = 0; j < 3; j++) { w.mean[j] = 0.0; w.m2[j] = 0.0; }
-  for (int j = 0; j < 9; j++) w.cov[j] = 0.0;
-  w.n = 0;
-}
-
-// normal_distributions.c:75-104, one sample.
-NDNET_FN void welford_update(Welford& w, const double* x) {
-  w.n++;
-  const double n = (double)w.n;
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const double old = w.mean[j];
-    w.mean[j] = w.mean[j] + (x[j] - w.mean[j]) / n;
-    w.m2[j] = w.m2[j] + (x[j] - old) * (x[j] - w.mean[j]);
-    double v = w.m2[j] / n;
-    w.cov[j * 3 + j] = (v != v) ? 0.0 : v;
-#pragma unroll
-    for (int k = j + 1; k < 3; k++) {
-      double c = w.cov[j * 3 + k] + (x[j] - w.mean[j]) * (x[k] - w.mean[k]) / n;
-      c = (c != c) ? 0.0 : c;
-      w.cov[j * 3 + k] = c;
-      w.cov[k * 3 + j] = c;
-    }
-  }
 }
 
 // gsl_linalg_LU_decomp for a 3x3 (GSL 2.7: LU_decomp_L2 via LU_decomp_L3):

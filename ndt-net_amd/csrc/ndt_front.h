@@ -554,7 +554,10 @@ __global__ void __launch_bounds__(kFrontThreads) k_front(const T* __restrict__ p
     double off[3] = {s.off[0], s.off[1], s.off[2]};
     uint32_t len[3] = {s.len[0], s.len[1], s.len[2]};
     // float points: keys screened in single precision (voxel_key_f32), valid
-    // when the grid offset is a float (it is the minimum of float points)
+    // when the grid offset is a float (it is the minimum of float points).
+    // The same five constants are derived in k_point_rows (ndt_point_rows.h)
+    // and in k_debug_voxel_keys (ndt_kernels.hip), which tests them: keep the
+    // three sites the same.
     const float off32[3] = {(float)off[0], (float)off[1], (float)off[2]};
     const float inv32 = (float)inv_vs;
     const float lenf[3] = {(float)len[0], (float)len[1], (float)len[2]};

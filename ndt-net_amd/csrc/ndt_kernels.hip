@@ -50,7 +50,8 @@
 //                     (ndt.c:28-73)
 //   k_point_rows      ndt_point_rows.h: the output row every input point was
 //                     folded into (ndnet_ndt_point_rows)
-//   k_set_epoch, k_debug_lu_chain
+//   k_set_epoch, k_debug_lu_chain, k_debug_log, k_debug_kl_pairs,
+//   k_debug_voxel_keys, k_debug_div_recip, k_debug_ord_keys
 //                     debug entry points
 //
 // The translation unit is compiled with -ffp-contract=off: every double
@@ -3696,6 +3697,111 @@ __global__ void __launch_bounds__(kKLThreads) k_kl_rank_sort(KLArgs A) {
 
 #include "ndt_prune.h"
 
+// ---- per-function debug kernels (ndnet_debug_*, for the parity tests) ----
+//
+// One element per thread, thread i of the grid handles element i, in
+// kDebugThreads-thread workgroups (so a test can place cases lane by lane of
+// a 64-lane wave).  Each calls the device function under test exactly as the
+// stage kernels above do; none is part of a run.
+constexpr int kDebugThreads = 256;
+
+// ndnet_debug_log: ndnet_log as kl_score calls it.
+__global__ void __launch_bounds__(kDebugThreads) k_debug_log(const double* x, uint32_t n, double* y) {
+  const uint32_t i = blockIdx.x * kDebugThreads + threadIdx.x;
+  if (i >= n) return;
+  y[i] = ndnet_log(x[i]);
+}
+
+// ndnet_debug_kl_pairs: lu3 on copies of P[i] and Q[i], then what kl_event
+// does from the two chain states (the n > 1 case): determinants, sign
+// determinants, the flag, and where it is 1 the inverse of Q's LU and the
+// score.
+__global__ void __launch_bounds__(kDebugThreads) k_debug_kl_pairs(const double* P, const double* Q, uint32_t n,
+                                                                  double* score, uint32_t* flag, double* inv_out) {
+  const uint32_t i = blockIdx.x * kDebugThreads + threadIdx.x;
+  if (i >= n) return;
+  double Lp[9], Lq[9];
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    Lp[j] = P[9 * (uint64_t)i + j];
+    Lq[j] = Q[9 * (uint64_t)i + j];
+  }
+  uint32_t pp, pq;
+  int sp, sq;
+  lu3(Lp, pp, sp);
+  lu3(Lq, pq, sq);
+  const uint32_t psq = pq | (sq < 0 ? 0x100u : 0u);  // as the chain stores it
+  uint32_t fl = 0;
+  double val = 0.0;
+  double inv[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const double pd = lu3_det(Lp, sp), qd = lu3_det(Lq, sq);
+  if (!(pd == 0 || qd == 0) && lu3_sgndet(Lp, sp) != 0 && lu3_sgndet(Lq, sq) != 0) {
+    fl = 1;
+    lu3_invert(Lq, psq & 0x3f, inv);
+    val = kl_score(Lp, Lq, psq & 0x3f, pd, qd);
+  }
+  flag[i] = fl;
+  score[i] = val;
+#pragma unroll
+  for (int j = 0; j < 9; j++) inv_out[9 * (uint64_t)i + j] = inv[j];
+}
+
+struct DebugGrid {
+  double off[3];
+  uint32_t len[3];
+  double vs;
+};
+
+// ndnet_debug_voxel_keys: voxel_key of the double point and voxel_key_f32 of
+// its float cast.  The float screen's constants are derived as k_front's
+// search passes (ndt_front.h) and k_point_rows (ndt_point_rows.h) derive
+// them: keep the three sites the same.  Every lane of a wave calls voxel_key
+// (it votes across the wave); lanes past n repeat the last point.
+__global__ void __launch_bounds__(kDebugThreads) k_debug_voxel_keys(const double* pts, uint32_t n, DebugGrid g,
+                                                                    uint32_t* key64, uint32_t* key32) {
+  const uint32_t i = blockIdx.x * kDebugThreads + threadIdx.x;
+  const uint64_t e = i < n ? i : n - 1;
+  const double x = pts[3 * e], y = pts[3 * e + 1], z = pts[3 * e + 2];
+  const double vs = g.vs, inv_vs = 1.0 / vs;
+  const double off[3] = {g.off[0], g.off[1], g.off[2]};
+  const uint32_t len[3] = {g.len[0], g.len[1], g.len[2]};
+  const float off32[3] = {(float)off[0], (float)off[1], (float)off[2]};
+  const float inv32 = (float)inv_vs;
+  const float lenf[3] = {(float)len[0], (float)len[1], (float)len[2]};
+  const float lmax = fmaxf(lenf[0], fmaxf(lenf[1], lenf[2]));
+  const float half_tol = 0.5f - lmax * 0x1p-19f;
+  const bool fast32 = (double)off32[0] == off[0] && (double)off32[1] == off[1] && (double)off32[2] == off[2];
+  const uint32_t k32 =
+      fast32 ? voxel_key_f32((float)x, (float)y, (float)z, off32, inv32, half_tol, lenf, len) : kKeyRedo;
+  const uint32_t k64 = voxel_key(x, y, z, off, len, vs, inv_vs);
+  if (i < n) {
+    key64[i] = k64;
+    key32[i] = k32;
+  }
+}
+
+// ndnet_debug_div_recip: the light fold's division t / n (div_fast on the
+// refined reciprocal of the count).
+__global__ void __launch_bounds__(kDebugThreads) k_debug_div_recip(const double* t, const uint32_t* cnt, uint32_t n,
+                                                                   double* q) {
+  const uint32_t i = blockIdx.x * kDebugThreads + threadIdx.x;
+  if (i >= n) return;
+  const double dn = (double)cnt[i];
+  q[i] = div_fast(t[i], dn, recip_refined(dn));
+}
+
+// ndnet_debug_ord_keys: the order-preserving keys of the limits and of the KL list.
+__global__ void __launch_bounds__(kDebugThreads) k_debug_ord_keys(const double* x, uint32_t n, unsigned long long* key,
+                                                                  double* back, unsigned long long* skey) {
+  const uint32_t i = blockIdx.x * kDebugThreads + threadIdx.x;
+  if (i >= n) return;
+  const double v = x[i];
+  const uint64_t k = ord_key(v);
+  key[i] = k;
+  back[i] = ord_unkey(k);
+  skey[i] = score_key(v);
+}
+
 // ------------------------------------------------------------------ host side
 
 #define HIPCHK(x)                                                             \
@@ -4468,6 +4574,64 @@ int ndnet_debug_lu_chain(const double* d_A, uint32_t n, int steps, double* d_sta
   if (!d_A || !d_states || !d_ps || !d_flags || steps <= 0 || steps > 12) return NDNET_ERR_ARG;
   if (n == 0) return NDNET_OK;
   k_debug_lu_chain<<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(d_A, n, steps, d_states, d_ps, d_flags);
+  HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_debug_log(const double* d_x, uint32_t n, double* d_y, void* stream) {
+  if (!d_x || !d_y) return NDNET_ERR_ARG;
+  if (n == 0) return NDNET_OK;
+  k_debug_log<<<(n + kDebugThreads - 1) / kDebugThreads, kDebugThreads, 0, (hipStream_t)stream>>>(d_x, n, d_y);
+  HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_debug_kl_pairs(const double* d_P, const double* d_Q, uint32_t n, double* d_score, uint32_t* d_flag,
+                         double* d_inv, void* stream) {
+  if (!d_P || !d_Q || !d_score || !d_flag || !d_inv) return NDNET_ERR_ARG;
+  if (n == 0) return NDNET_OK;
+  k_debug_kl_pairs<<<(n + kDebugThreads - 1) / kDebugThreads, kDebugThreads, 0, (hipStream_t)stream>>>(
+      d_P, d_Q, n, d_score, d_flag, d_inv);
+  HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_debug_voxel_keys(const double* d_pts64, uint32_t n, const double* off, const uint32_t* len, double vs,
+                           uint32_t* d_key64, uint32_t* d_key32, void* stream) {
+  if (!d_pts64 || !off || !len || !d_key64 || !d_key32 || !(vs > 0.0)) return NDNET_ERR_ARG;
+  DebugGrid g;
+  uint64_t cells = 1;
+  for (int a = 0; a < 3; a++) {
+    if (len[a] == 0 || len[a] > 65535u) return NDNET_ERR_ARG;
+    if ((double)(float)off[a] != off[a]) return NDNET_ERR_ARG;  // fast32: the offsets are floats
+    cells *= len[a];
+    g.off[a] = off[a];
+    g.len[a] = len[a];
+  }
+  if (cells >= kKeyRedo) return NDNET_ERR_ARG;  // a key is a uint32 below the two marker values
+  g.vs = vs;
+  if (n == 0) return NDNET_OK;
+  k_debug_voxel_keys<<<(n + kDebugThreads - 1) / kDebugThreads, kDebugThreads, 0, (hipStream_t)stream>>>(
+      d_pts64, n, g, d_key64, d_key32);
+  HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_debug_div_recip(const double* d_t, const uint32_t* d_n, uint32_t count, double* d_q, void* stream) {
+  if (!d_t || !d_n || !d_q) return NDNET_ERR_ARG;
+  if (count == 0) return NDNET_OK;
+  k_debug_div_recip<<<(count + kDebugThreads - 1) / kDebugThreads, kDebugThreads, 0, (hipStream_t)stream>>>(
+      d_t, d_n, count, d_q);
+  HIPCHK(hipGetLastError());
+  return NDNET_OK;
+}
+
+int ndnet_debug_ord_keys(const double* d_x, uint32_t n, unsigned long long* d_key, double* d_back,
+                         unsigned long long* d_score_key, void* stream) {
+  if (!d_x || !d_key || !d_back || !d_score_key) return NDNET_ERR_ARG;
+  if (n == 0) return NDNET_OK;
+  k_debug_ord_keys<<<(n + kDebugThreads - 1) / kDebugThreads, kDebugThreads, 0, (hipStream_t)stream>>>(
+      d_x, n, d_key, d_back, d_score_key);
   HIPCHK(hipGetLastError());
   return NDNET_OK;
 }

@@ -8,7 +8,9 @@
 // bit casts, evaluated in double-double (error ~2^-70 relative), then rounded
 // once -- i.e. correctly rounded except in vanishingly rare cases.  glibc's log
 // is itself within 0.52 ulp, so the two agree on all but ~1% of inputs, by one
-// ulp (tests/test_log.py measures this).
+// ulp (tests/test_oracle.py test_portable_log_correctly_rounded measures this
+// on the host; tests/test_ndt_device_gpu.py checks the gfx950 build gives the
+// host's bits).
 //
 // Callers define NDNET_FN (e.g. `__device__ static inline`) and NDNET_TABQ
 // (e.g. `__constant__`) before including; both default to host inline.

@@ -115,7 +115,9 @@ __global__ void __launch_bounds__(kPrThreads) k_point_rows(const float* __restri
     }
   }
   __syncthreads();
-  // the key constants as k_front's search passes derive them
+  // the key constants as k_front's search passes (ndt_front.h) and
+  // k_debug_voxel_keys (ndt_kernels.hip, the tested copy) derive them: keep
+  // the three sites the same
   const double vs = c.vs, inv_vs = 1.0 / vs;
   const double off[3] = {c.off[0], c.off[1], c.off[2]};
   const uint32_t len[3] = {c.len[0], c.len[1], c.len[2]};

@@ -139,6 +139,12 @@ EXPORTS = {
     "ndnet_ndt_debug_front_marks": (_I, [_P, _P]),
     "ndnet_ndt_debug_wq_marks": (_I, [_P, _P, ctypes.POINTER(ctypes.c_uint32)]),
     "ndnet_debug_lu_chain": (_I, [_P, ctypes.c_uint32, _I, _P, _P, _P, _P]),
+    "ndnet_debug_log": (_I, [_P, ctypes.c_uint32, _P, _P]),
+    "ndnet_debug_kl_pairs": (_I, [_P, _P, ctypes.c_uint32, _P, _P, _P, _P]),
+    "ndnet_debug_voxel_keys": (_I, [_P, ctypes.c_uint32, _PD, ctypes.POINTER(ctypes.c_uint32), ctypes.c_double, _P, _P,
+                                    _P]),
+    "ndnet_debug_div_recip": (_I, [_P, _P, ctypes.c_uint32, _P, _P]),
+    "ndnet_debug_ord_keys": (_I, [_P, ctypes.c_uint32, _P, _P, _P, _P]),
     "ndnet_ndt_debug_front_wg_marks": (_I, [_P, _P, ctypes.POINTER(_I)]),
     "ndnet_ndt_set_timing": (_I, [_P, _I]),
     "ndnet_ndt_stage_ms": (_I, [_P, _P]),

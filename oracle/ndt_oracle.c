@@ -734,7 +734,8 @@ void free_nds(orc_nd* nd_array, unsigned long num_nds) {
 
 void free_kl_divergences(orc_kl* kl) { free(kl); }
 
-/* portable log, exposed for tests/test_log.py */
+/* portable log, exposed for tests/test_oracle.py (test_portable_log_correctly_rounded)
+ * and tests/test_ndt_device_gpu.py (the device build, bit for bit) */
 double orc_portable_log(double x) { return ndnet_log(x); }
 void orc_portable_log_many(const double* x, double* y, uint64_t n) {
   for (uint64_t i = 0; i < n; i++) y[i] = ndnet_log(x[i]);
@@ -802,5 +803,54 @@ void orc_lu_chain(const double* A, uint64_t n, int steps, double* states, uint32
       ps[m * steps + t] = (uint32_t)perm[0] | ((uint32_t)perm[1] << 2) | ((uint32_t)perm[2] << 4) | (sg < 0 ? 0x100u : 0u);
       flags[m * steps + t] = (orc_lu_det(S, sg) != 0 && orc_lu_sgndet(S, sg) != 0) ? 1u : 0u;
     }
+  }
+}
+
+/* One KL event per matrix pair, for the device's ndnet_debug_kl_pairs
+ * (tests/test_ndt_device_*.py): gsl_linalg_LU_decomp of a copy of P[m] and of
+ * Q[m], then kl_divergence from there on (kullback_leibler.c:57-115, both
+ * counts above 1) with the portable log whatever orc_use_portable_log says.
+ * flag[m] = 1 where the event exists (no determinant or sign determinant is
+ * zero); there inv[m] is gsl_linalg_LU_invert of Q's LU and score[m] the
+ * divergence; elsewhere both are 0. */
+void orc_kl_pairs(const double* P, const double* Q, uint64_t n, double* score, uint32_t* flag, double* inv) {
+  for (uint64_t m = 0; m < n; m++) {
+    double Lp[9], Lq[9], qinv[9];
+    int pperm[3], qperm[3], ps, qs;
+    memcpy(Lp, P + 9 * m, sizeof Lp);
+    memcpy(Lq, Q + 9 * m, sizeof Lq);
+    flag[m] = 0;
+    score[m] = 0.0;
+    for (int j = 0; j < 9; j++) inv[9 * m + j] = 0.0;
+    orc_lu_decomp(Lp, pperm, &ps);
+    orc_lu_decomp(Lq, qperm, &qs);
+    const double pd = orc_lu_det(Lp, ps);
+    const double qd = orc_lu_det(Lq, qs);
+    if (pd == 0 || qd == 0) continue;
+    if (orc_lu_sgndet(Lp, ps) == 0 || orc_lu_sgndet(Lq, qs) == 0) continue;
+    orc_lu_invert_gsl(Lq, qperm, qinv);
+    /* the dgemm-order trace of orc_kl_divergence */
+    double tr = 0;
+    for (int i = 0; i < 3; i++) {
+      double cii = 0.0;
+      for (int kk = 0; kk < 3; kk++) {
+        const double t = 1.0 * qinv[i * 3 + kk];
+        if (t != 0.0) cii += t * Lp[kk * 3 + i];
+      }
+      tr += cii;
+    }
+    const double first = 0.0;
+    flag[m] = 1;
+    score[m] = 0.5 * (first + tr - ndnet_log(qd / pd) - 3);
+    memcpy(inv + 9 * m, qinv, sizeof qinv);
+  }
+}
+
+/* orc_voxel_index over n points pts[n][3]: key[i] = the linear index, or
+ * 0xffffffff where the point is out of grid. */
+void orc_voxel_keys(const double* pts, uint64_t n, const double* off, const int* len, double vs, uint32_t* key) {
+  for (uint64_t i = 0; i < n; i++) {
+    uint64_t idx;
+    key[i] = orc_voxel_index(pts + 3 * i, vs, len, off, &idx) < 0 ? 0xffffffffu : (uint32_t)idx;
   }
 }

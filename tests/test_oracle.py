@@ -109,11 +109,17 @@ def test_reference_threads_counts_and_means():
 
 
 def test_portable_log_correctly_rounded():
+    """On this test's own mixture and on every positive finite input of the
+    device test's corpus (tests/ndt_device_cases.py log_cases: table-index
+    edges, the sqrt(2) split, extreme mantissas, subnormals)."""
     import decimal
+    import ndt_device_cases as C
     decimal.getcontext().prec = 50
     rng = np.random.default_rng(1)
+    corpus = C.log_cases()
     x = np.concatenate([np.exp(rng.uniform(-700, 700, 3000)), rng.uniform(0.5, 2.0, 3000),
-                        1 + rng.normal(0, 1e-9, 500), [1.0, 2.0, 0.5, 1e-310, 5e-324, 1.7976931348623157e308]])
+                        1 + rng.normal(0, 1e-9, 500), [1.0, 2.0, 0.5, 1e-310, 5e-324, 1.7976931348623157e308],
+                        corpus[C.log_positive_finite(corpus)]])
     y = np.zeros_like(x)
     g = np.zeros_like(x)
     O.lib().orc_portable_log_many(O._ptr(x), O._ptr(y), ctypes.c_uint64(len(x)))
