@@ -261,7 +261,8 @@ def test_per_cloud_weights_and_bias():
     assert (c.ref[1] - c.ref[0]).abs().max() > 1.0  # the clouds' results do differ
 
 
-def _softmax_case(oc, variant):
+def _softmax_inputs(oc, variant):
+    """(x, layers) of one log_softmax case, on the CPU."""
     g = _gen(700 + oc)
     n = _ph()._npad(oc)
     layers = [_layer(g, 16, 64, F32, 1, k_used=12), _layer(g, 64, 128, X6, 1), _layer(g, 128, n, X6, 0, n_used=oc)]
@@ -275,7 +276,12 @@ def _softmax_case(oc, variant):
         layers[2]["b"] *= 90.0 / top
     if variant == "pad100":  # padded columns must not enter the sum
         layers[2]["b"][oc:] = 100.0
-    return _Case(x, 12, layers, 1, out_cols=oc)
+    return x, layers
+
+
+def _softmax_case(oc, variant, case=None):
+    x, layers = _softmax_inputs(oc, variant)
+    return (case or _Case)(x, 12, layers, 1, out_cols=oc)
 
 
 @pytest.mark.gpu
@@ -345,6 +351,17 @@ def _run_checked(c, name, entry, bad):
     _report(f"{name} {entry[9:]} out", got, c.ref, c.e_t, bad)
 
 
+def _head_parts(g, B, head_K, kin, nout):
+    """The head prologue's operands and float64 results on the CPU: (h2, w3, b3, basis, t1, W0^T [B][16][nout])."""
+    h2 = torch.relu(torch.randn(B, head_K, generator=g) + 1.0)
+    w3, b3 = torch.randn(9, head_K, generator=g) / math.sqrt(head_K), torch.randn(9, generator=g) * 0.5
+    basis = torch.randn(9, kin * nout, generator=g) / 3.0
+    t1_ref = h2.double() @ w3.double().t() + b3.double()
+    w_ref = torch.nn.functional.pad((t1_ref @ basis.double()).view(B, kin, nout), (0, 0, 0, 16 - kin))
+    assert (t1_ref[1:] - t1_ref[:-1]).abs().amax(dim=1).min() > 1e-3  # the clouds differ
+    return h2, w3, b3, basis, t1_ref, w_ref
+
+
 class _Head:
     """The head prologue's operands for B clouds: h2 (non-negative, rows of
     head_K + 4 floats with NaN pads), W3, b3 and a dense basis [9][kin * nout]
@@ -354,13 +371,8 @@ class _Head:
 
     def __init__(self, g, B, head_K, kin, nout):
         self.B, self.K, self.kin, self.nout, self.ld = B, head_K, kin, nout, head_K + 4
-        h2 = torch.relu(torch.randn(B, head_K, generator=g) + 1.0)
-        w3, b3 = torch.randn(9, head_K, generator=g) / math.sqrt(head_K), torch.randn(9, generator=g) * 0.5
-        basis = torch.randn(9, kin * nout, generator=g) / 3.0
+        h2, w3, b3, basis, self.t1_ref, self.w_ref = _head_parts(g, B, head_K, kin, nout)
         pad = (0, 0, 0, 16 - kin)
-        self.t1_ref = h2.double() @ w3.double().t() + b3.double()
-        self.w_ref = torch.nn.functional.pad((self.t1_ref @ basis.double()).view(B, kin, nout), pad)
-        assert (self.t1_ref[1:] - self.t1_ref[:-1]).abs().amax(dim=1).min() > 1e-3  # the clouds differ
         self.h2, self.w3, self.b3, self.basis = _padded(h2, self.ld).cuda(), w3.cuda(), b3.cuda(), basis.cuda()
         t1_t = torch.addmm(self.b3, h2.cuda(), self.w3.t())
         self.w_t = torch.nn.functional.pad(torch.matmul(t1_t, self.basis).view(B, kin, nout), pad)
@@ -441,6 +453,19 @@ def test_head_prologue_mfma_layer0(case, N):
     hd.check(c, f"head mfma {case} N={N}")
 
 
+def _fold_parts(seed, N, prec1):
+    """The fold_t2 prologue's operands for 3 clouds on the CPU: (w0 [3][12][64], b0, t2 [3][64][64], the folded
+    layer 0 in float64 -- W0' [3][16][64], b0' [3][64] --, the layers after it, x)."""
+    g = _gen(seed)
+    w0 = torch.randn(3, 12, 64, generator=g) / math.sqrt(12)
+    b0, t2 = torch.randn(64, generator=g) * 0.5, torch.randn(3, 64, 64, generator=g) / 8.0
+    w_ref = torch.nn.functional.pad(w0.double() @ t2.double(), (0, 0, 0, 4))
+    b_ref = b0.double() @ t2.double()                                   # [B][64]
+    assert (b_ref[1:] - b_ref[:-1]).abs().amax(dim=1).min() > 1e-3      # the clouds differ
+    tail = [_layer(g, 64, 128, prec1, 1), _layer(g, 128, 64, F32, 0)]
+    return w0, b0, t2, w_ref, b_ref, tail, _nd_rows(3, N, g)
+
+
 class _Fold:
     """The fold_t2 prologue's operands for 3 clouds: a per-cloud layer 0 (W0^T
     [12][64] in a K = 16 fragment, bias b0) and a dense t2 per cloud in rows
@@ -448,16 +473,11 @@ class _Fold:
     64, pooled.  float64: layer 0 is W0'[b] = W0^T[b] t2[b], b0'[b] = b0^T
     t2[b], its relu flag applied after."""
 
-    def __init__(self, seed, N, relu0, prec1, fold_ld, prefill=None):
+    def __init__(self, seed, N, relu0, prec1, fold_ld, prefill=None, case=None):
         ph = _ph()
-        g = _gen(seed)
         B = self.B = 3
-        w0 = torch.randn(B, 12, 64, generator=g) / math.sqrt(12)
-        b0, t2 = torch.randn(64, generator=g) * 0.5, torch.randn(B, 64, 64, generator=g) / 8.0
+        w0, b0, t2, self.w_ref, self.b_ref, tail, self.x = _fold_parts(seed, N, prec1)
         pad = (0, 0, 0, 4)
-        self.w_ref = torch.nn.functional.pad(w0.double() @ t2.double(), pad)
-        self.b_ref = b0.double() @ t2.double()                                   # [B][64]
-        assert (self.b_ref[1:] - self.b_ref[:-1]).abs().amax(dim=1).min() > 1e-3  # the clouds differ
         self.w0f = ph._frag(torch.nn.functional.pad(w0, pad)).cuda()             # [B][1024]
         self.b0, t2d = b0.cuda(), t2.cuda()
         self.t2, self.fold_ld = _padded(t2.view(B, 4096), fold_ld).cuda(), fold_ld
@@ -466,9 +486,8 @@ class _Fold:
         self.e_w = (w_t.double().cpu() - self.w_ref).abs().max().item()
         self.e_b = (b_t.double().cpu() - self.b_ref).abs().max().item()
         l0 = dict(wT=self.w_ref, b=self.b_ref, K=16, N=64, prec=F32, relu=relu0, fuse=False, dev=(w_t, b_t))
-        self.layers = [l0, _layer(g, 64, 128, prec1, 1), _layer(g, 128, 64, F32, 0)]
-        self.x = _nd_rows(B, N, g)
-        c = self.c = _Case(self.x, 12, self.layers, 0)
+        self.layers = [l0] + tail
+        c = self.c = (case or _Case)(self.x, 12, self.layers, 0)
         # the HIP chain: the untransformed layer 0 and t2
         L0 = c.ch.L[0]
         L0.w, L0.w_cloud_stride, L0.bias, L0.bias_cloud_stride = self.w0f.data_ptr(), 1024, self.b0.data_ptr(), 0

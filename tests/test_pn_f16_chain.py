@@ -191,25 +191,27 @@ def test_accuracy_against_float64(shape, B, N):
     assert not bad, bad
 
 
-def _edge_scales(base, in_cols, mats):
+def _edge_scales(base, in_cols, mats, target=1.05 * LO):
     """mats: (W^T in float64, relu, feeds a split layer) per layer -> the factor of each layer's weights that
-    puts row 0's maximum at its output at 1.05 * 2^-4 where that output is a split layer's input (else 1)."""
+    puts row 0's maximum at its output at `target` (1.05 * 2^-4) where that output is a split layer's input
+    (else 1)."""
     h = torch.nn.functional.pad(base[:, :in_cols].double(), (0, mats[0][0].shape[0] - in_cols))
     out = []
     for w, relu, feeds in mats:
         o = torch.matmul(h, w)
         o = torch.relu(o) if relu else o
-        s = 1.05 * LO / o[0].abs().max().item() if feeds else 1.0
+        s = target / o[0].abs().max().item() if feeds else 1.0
         out.append(s)
         h = o * s
     return out
 
 
-def _lower_edge_case(shape, B, N, g):
+def _lower_edge_case(shape, B, N, g, target=1.05 * LO):
     """Zero biases (the chain is then positively homogeneous), rows of period 32 -- so every tile of either
     build holds the same rows, the ragged tail a prefix of them -- whose row 0 is 8 times the others, and
-    each layer's weights rescaled so that row 0's maximum at its output is 1.05 * 2^-4: every split layer's
-    tile maximum then sits just above the window's lower edge (the caller checks it), most elements below 2^-6."""
+    each layer's weights rescaled so that row 0's maximum at its output is `target`, 1.05 * 2^-4: every split
+    layer's tile maximum then sits just above the window's lower edge (the caller checks it), most elements
+    below 2^-6.  (tests/test_pn_f16_shapes.py puts them below the upper edge with target = 0.9 * 2^11.)"""
     base = _nd_rows(1, 32, g)[0]
     base[1:] *= 0.125
     x = base[torch.arange(N) % 32].unsqueeze(0).repeat(B, 1, 1).contiguous()
@@ -220,13 +222,13 @@ def _lower_edge_case(shape, B, N, g):
         tail = parts["tail"]
         mats = [(parts["hd"].w_ref[0] @ parts["m"].double(), 1, True), (tail[0]["wT"].double(), 1, True),
                 (tail[1]["wT"].double(), 1, False)]
-        s = _edge_scales(base, 12, mats)
+        s = _edge_scales(base, 12, mats, target)
         parts["m"] *= s[0]
         tail[0]["wT"] *= s[1]
         return x, 12, _b_layers(parts), 0, 0, parts
     in_cols, layers, mode, out_cols = _chain_layers(shape, g, zero_bias=True)
     feeds = [l + 1 < len(layers) and layers[l + 1]["prec"] == X6 for l in range(len(layers))]
-    for L, s in zip(layers, _edge_scales(base, in_cols, [(L["wT"].double(), L["relu"], f) for L, f in zip(layers, feeds)])):
+    for L, s in zip(layers, _edge_scales(base, in_cols, [(L["wT"].double(), L["relu"], f) for L, f in zip(layers, feeds)], target)):
         L["wT"] *= s
     return x, in_cols, layers, mode, out_cols, None
 
