@@ -64,6 +64,20 @@ class AugConfig(ctypes.Structure):
 
 
 assert ctypes.sizeof(AugConfig) == 80
+
+
+class SampleConfig(ctypes.Structure):
+    """ndnet_sample_config (include/ndnet_sample.h)."""
+    _fields_ = [
+        ("seed", ctypes.c_uint32),
+        ("stream", ctypes.c_uint32),
+        ("key_bits", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(SampleConfig) == 12
+SAMPLE_TILE = 1024  # NDNET_SAMPLE_* (include/ndnet_sample.h)
+SAMPLE_LIST = 1024
 AUG_TILE = 1024  # NDNET_AUG_TILE (include/ndnet_augment.h)
 NN_TILE_POINTS = 1024  # NDNET_NN_* (include/ndnet_nearest.h)
 NN_CHUNK_SAMPLES = 1024
@@ -128,6 +142,10 @@ EXPORTS = {
     # include/ndnet_augment.h
     "ndnet_aug_work_bytes": (ctypes.c_size_t, [_I, _U64]),
     "ndnet_aug_run": (_I, [_P, _P, _P, _P, _I, _U64, _P, _P, _P, _P, _P, _P, _P]),
+    # include/ndnet_sample.h
+    "ndnet_sample_work_bytes": (ctypes.c_size_t, [_I, _U64]),
+    "ndnet_sample_random_run": (_I, [_P, _P, _P, _P, _I, _U64, _U64, ctypes.c_int32, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ndnet_sample_gather_run": (_I, [_P, _P, _P, _I, _U64, _U64, ctypes.c_int32, _P, _P, _P, _P]),
     # include/ndnet_packed.h
     "ndnet_pts_unpack_i16": (_I, [_P, _P, _I, _U64, _P, _P, _P]),
     "ndnet_ndt_debug_dump": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

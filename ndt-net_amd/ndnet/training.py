@@ -378,6 +378,69 @@ class Trainer:
         return (g.s_points, g.s_gt, g.s_counts) if counts else (g.s_points, g.s_gt)
 
 
+def _capture_step(model: torch.nn.Module, opt, dev, body, counters=(), warmup: int = 3):
+    """``body()`` -- a whole training step on static buffers -- captured into
+    one HIP graph: ``(graph, body's return value)``.  Capture needs the step's
+    lazy state to exist (library handles, MIOpen's algorithm choices, the
+    gradients and Adam's moments), so ``warmup`` steps run eagerly on a side
+    stream first; the parameters, the buffers, the optimizer state and the
+    device ``counters`` (the step tensors of an ``Augment`` or a
+    ``RandomSample``) are snapshotted before them and restored after the
+    capture, so the first replay is the trainer's first step and draw 0."""
+    with torch.no_grad():
+        params = [p.detach().clone() for p in model.parameters()]
+        bufs = [b.detach().clone() for b in model.buffers()]
+        saved = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in opt.state.items()}
+        steps = [c.clone() for c in counters]
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for _ in range(max(1, int(warmup))):
+            opt.zero_grad(set_to_none=True)
+            body()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize(dev)
+    opt.zero_grad(set_to_none=True)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = body()
+    with torch.no_grad():
+        for p, s in zip(model.parameters(), params):
+            p.copy_(s)
+        for b, s in zip(model.buffers(), bufs):
+            b.copy_(s)
+        for p, st in opt.state.items():
+            before = saved.get(p, {})
+            for k, v in st.items():
+                if torch.is_tensor(v):
+                    if k in before:
+                        v.copy_(before[k])
+                    else:
+                        v.zero_()  # a fresh moment / step count
+        for c, s in zip(counters, steps):
+            c.copy_(s)  # the warm-up's draws are rolled back
+    torch.cuda.synchronize(dev)
+    return graph, out
+
+
+def _replay_step(step, points: torch.Tensor, gt_points: torch.Tensor, counts) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The inputs into ``step``'s static buffers (unless they are those
+    buffers) and one replay of its graph: ``(loss, accuracy)``."""
+    if (counts is not None) != (step.s_counts is not None):
+        raise ValueError("counts go with a step captured with ragged=True, and only with it")
+    # the replay does not run Python: flip the mode here, so an eval forward
+    # after it re-folds the updated weights (NDTNetSegmentation.train)
+    step.tr.model.train()
+    if points.data_ptr() != step.s_points.data_ptr():
+        step.s_points.copy_(points, non_blocking=True)
+    if gt_points.data_ptr() != step.s_gt.data_ptr():
+        step.s_gt.copy_(gt_points, non_blocking=True)
+    if counts is not None and not (torch.is_tensor(counts) and counts.data_ptr() == step.s_counts.data_ptr()):
+        step.s_counts.copy_(torch.as_tensor(counts).to(torch.int32), non_blocking=True)
+    step.graph.replay()
+    return step.loss, step.acc
+
+
 class GraphedTrainStep:
     """tools/train.py:67-81 for one input shape, captured once and replayed:
     ndt_preprocessing with labels (HIP) -> train-mode forward -> NLL loss ->
@@ -414,40 +477,8 @@ class GraphedTrainStep:
         # a non-degenerate cloud for the warm-up steps (zeros would be one voxel)
         gen = torch.Generator(device=dev).manual_seed(0)
         self.s_points.copy_(torch.rand(self.s_points.shape, device=dev, generator=gen) * 20 - 10)
-        model, opt = tr.model, tr.opt
-        with torch.no_grad():
-            params = [p.detach().clone() for p in model.parameters()]
-            bufs = [b.detach().clone() for b in model.buffers()]
-            saved = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in opt.state.items()}
-            aug_step = tr.augment.step_tensor(dev).clone() if tr.augment is not None else None
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(1, int(warmup))):
-                opt.zero_grad(set_to_none=True)
-                self._body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        opt.zero_grad(set_to_none=True)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.loss, self.acc = self._body()
-        with torch.no_grad():
-            for p, s in zip(model.parameters(), params):
-                p.copy_(s)
-            for b, s in zip(model.buffers(), bufs):
-                b.copy_(s)
-            for p, st in opt.state.items():
-                before = saved.get(p, {})
-                for k, v in st.items():
-                    if torch.is_tensor(v):
-                        if k in before:
-                            v.copy_(before[k])
-                        else:
-                            v.zero_()  # a fresh moment / step count
-            if aug_step is not None:
-                tr.augment.step_tensor(dev).copy_(aug_step)  # the warm-up's draws are rolled back
-        torch.cuda.synchronize(dev)
+        counters = [tr.augment.step_tensor(dev)] if tr.augment is not None else []
+        self.graph, (self.loss, self.acc) = _capture_step(tr.model, tr.opt, dev, self._body, counters, warmup)
 
     def _body(self):
         tr = self.tr
@@ -462,16 +493,271 @@ class GraphedTrainStep:
 
     def __call__(self, points: torch.Tensor, gt_points: torch.Tensor,
                  counts=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        if (counts is not None) != (self.s_counts is not None):
-            raise ValueError("counts go with a step captured with ragged=True, and only with it")
-        # the replay does not run Python: flip the mode here, so an eval forward
-        # after it re-folds the updated weights (NDTNetSegmentation.train)
-        self.tr.model.train()
-        if points.data_ptr() != self.s_points.data_ptr():
-            self.s_points.copy_(points, non_blocking=True)
-        if gt_points.data_ptr() != self.s_gt.data_ptr():
-            self.s_gt.copy_(gt_points, non_blocking=True)
-        if counts is not None and not (torch.is_tensor(counts) and counts.data_ptr() == self.s_counts.data_ptr()):
-            self.s_counts.copy_(torch.as_tensor(counts).to(torch.int32), non_blocking=True)
-        self.graph.replay()
-        return self.loss, self.acc
+        return _replay_step(self, points, gt_points, counts)
+
+
+class _BaselineBuffers:
+    """Every intermediate of the baseline step's front -- sampler, rows,
+    histogram -- for one batch shape, allocated once (the captured step)."""
+
+    def __init__(self, B: int, n: int, S: int, cols: int, device, sampler: str, loss: str) -> None:
+        i32 = dict(dtype=torch.int32, device=device)
+        self.samples = torch.empty((B, S, 3), dtype=torch.float32, device=device)
+        self.sample_labels = torch.empty((B, S), **i32)
+        self.sample_counts = torch.empty((B,), **i32)
+        self.indices = torch.empty((B, S), **i32)
+        self.min_dist = torch.empty((B, n), dtype=torch.float32, device=device) if sampler == "fps" else None
+        self.rows = torch.empty((B, n), **i32) if loss == "points" else None
+        self.hist = torch.empty((B, S, cols), **i32)
+
+
+class BaselineTrainer:
+    """The PointNet baseline's training step: one ``PointNetSegmentation`` +
+    Adam (+ DDP when a process group is active), on whole (ragged) scans.
+
+    A training step is: the trainer's ``Augment``, if it has one (its device
+    counts feed the sampler) -> the sampler -> the train-mode forward on the
+    HIP train blocks -> the loss on integer labels -> backward -> Adam.
+
+    ``sampler="random"`` (the reference's ``np.random.choice`` cut, on the
+    GPU): a ``RandomSample(n_samples, seed)`` the trainer owns
+    (``self.random_sample``).  ``sampler="fps"``: ``farthest_point_sample``
+    and ``gather_samples`` -- what the evaluation samples with, at some 30
+    times the cost of the rest of the step at 16 x 100k.
+
+    ``loss="samples"`` (the reference's objective): every existing sample is
+    scored against its own label -- ``point_loss`` on the histogram of the
+    sample labels over the rows ``0 .. S - 1``; the filler rows of a short
+    cloud carry label -1 and no weight.  ``loss="points"`` (what
+    ``segment.segment_points_fps`` is scored by): every point of the
+    (augmented) scan is scored under its nearest sample
+    (``nearest_sample`` -> ``row_histogram`` -> ``point_loss``), exactly the
+    mean NLL of what the evaluation would predict for every labelled point.
+    A label equal to ``ignore_label`` or outside ``0 .. num_classes`` carries
+    no weight under either.
+
+    ``step``, ``step_graphed``, ``graph_inputs`` and ``set_epoch`` are
+    ``Trainer``'s: labels one-hot ``[B, n, C + 1]`` or integer ids ``[B, n]``,
+    ``counts`` for a ragged batch, ``graphs=True`` (one GPU, no DDP) replays
+    the whole step as one HIP graph with the learning rate in a device tensor.
+    A trainer captures ONE step: the first batch fixes the points' shape, the
+    label form and whether counts come with it, and a batch of another shape
+    is a ``ValueError`` -- pad ragged scans to one length and give ``counts``,
+    which one graph serves whatever they are.  (Several captured steps in one
+    trainer share its gradients, optimizer state, sampler scratch and
+    counters; that is not supported here.)  ``step(train=False)`` never augments, runs the eval
+    forward (the HIP chains) and samples with a counter of its own fixed at
+    ``2^61`` that never advances: validation is deterministic, leaves the
+    training draws alone and updates nothing."""
+
+    SAMPLERS = ("random", "fps")
+    LOSSES = ("samples", "points")
+    EVAL_STEP = 1 << 61
+
+    def __init__(self, model: torch.nn.Module, lr: float, n_samples: int, num_classes: int,
+                 device: torch.device, ddp: Optional[bool] = None, bucket_cap_mb: float = 4.0,
+                 graphs: bool = False, sampler: str = "random", loss: str = "samples",
+                 ignore_label: int = -1, augment=None, seed: int = 0) -> None:
+        if sampler not in self.SAMPLERS:  # (checked before any GPU work)
+            raise ValueError(f"sampler must be one of {self.SAMPLERS}, got {sampler!r}")
+        if loss not in self.LOSSES:
+            raise ValueError(f"loss must be one of {self.LOSSES}, got {loss!r}")
+        if augment is not None:
+            from .augment import Augment
+            if not isinstance(augment, Augment):
+                raise ValueError(f"augment must be an ndnet.augment.Augment, got {type(augment).__name__}")
+        from .preprocessing.sample import RandomSample
+        self.random_sample = RandomSample(n_samples, seed)  # (validates n_samples and seed)
+        self.augment = augment
+        self.sampler, self.loss, self.ignore_label = sampler, loss, int(ignore_label)
+        import torch.distributed as dist
+        device = torch.device(device)
+        self.model = model.to(device)
+        self.device = device
+        self.n_samples, self.num_classes = int(n_samples), int(num_classes)
+        self.base_lr = float(lr)
+        if ddp is None:
+            ddp = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if graphs and (ddp or device.type != "cuda"):
+            raise ValueError("graphs=True needs one GPU and no DDP (the gradient all-reduce is not captured)")
+        self.graphs = bool(graphs)
+        self._graphed: dict = {}
+        self._iota: dict = {}
+        self._eval_step: Optional[torch.Tensor] = None
+        if ddp:
+            from torch.nn.parallel import DistributedDataParallel as DDP
+            ids = [device.index if device.index is not None else torch.cuda.current_device()] \
+                if device.type == "cuda" else None
+            self.net = DDP(self.model, device_ids=ids, bucket_cap_mb=bucket_cap_mb, gradient_as_bucket_view=True)
+        else:
+            self.net = self.model
+        if self.graphs:
+            self.opt = HipAdam(self.model.parameters(), lr=torch.tensor(self.base_lr, device=device))
+        else:
+            self.opt = torch.optim.Adam(self.model.parameters(), lr=self.base_lr)
+        self.random_sample.resolve_stream()  # (after the DDP set-up: the rank by default)
+        if augment is not None:
+            augment.resolve_stream()
+
+    set_epoch = Trainer.set_epoch
+
+    def _rows_iota(self, B: int) -> torch.Tensor:
+        """Row t of every cloud is sample t: the rows of ``loss="samples"``."""
+        r = self._iota.get(B)
+        if r is None:
+            r = self._iota[B] = torch.arange(self.n_samples, dtype=torch.int32, device=self.device).repeat(B, 1)
+        return r
+
+    def samples_and_targets(self, points: torch.Tensor, gt_points: torch.Tensor, counts=None, *,
+                            train: bool = True, buffers: Optional[_BaselineBuffers] = None):
+        """The front of a step, all on the GPU: ``(samples [B, S, 3], hist
+        [B, S, C + 1] int32, sample_counts [B] int32)``.  ``train=True`` puts
+        the trainer's ``Augment`` in front and advances the sampler's counter;
+        ``train=False`` draws from the eval counter and leaves it.  The eager
+        and the captured step both run this."""
+        from . import segment
+        from .preprocessing.ndtnet_preprocessing import check_class_ids, check_counts, class_ids
+        from .preprocessing.sample import gather_samples
+        check_class_ids(gt_points, points)
+        if points.dim() != 3 or points.shape[-1] != 3:
+            raise ValueError(f"points must be [B, n, 3], got {tuple(points.shape)}")
+        B, n, _ = points.shape
+        S, dev, buf = self.n_samples, self.device, buffers
+        if S > n:
+            raise ValueError(f"n_samples = {S} needs scans padded to at least that many points, got n = {n}")
+        if counts is not None:
+            check_counts(counts, B, n)
+            counts = torch.as_tensor(counts).to(device=dev, dtype=torch.int32).contiguous()
+        pts = points.to(device=dev, dtype=torch.float32).contiguous()
+        labels = class_ids(gt_points, dev)  # ids as they come, or ndnet_row_argmax of a one-hot
+        if train and self.augment is not None:
+            pts, labels, kept = self.augment(pts, labels, counts)
+            if counts is not None or self.augment.drop > 0:
+                counts = kept
+        out = {} if buf is None else dict(out_points=buf.samples, out_labels=buf.sample_labels,
+                                          out_counts=buf.sample_counts)
+        if self.sampler == "random":
+            if not train and self._eval_step is None:
+                self._eval_step = torch.tensor([self.EVAL_STEP], dtype=torch.int64, device=dev)
+            smp, slab, scnt, _ = self.random_sample(
+                pts, labels, counts, advance=train, step=None if train else self._eval_step,
+                out_indices=None if buf is None else buf.indices, **out)
+        else:
+            from .preprocessing.fps import farthest_point_sample
+            idx = farthest_point_sample(pts, S, counts=counts, out=None if buf is None else buf.indices,
+                                        min_dist=None if buf is None else buf.min_dist)
+            smp, slab, scnt = gather_samples(pts, idx, labels, **out)
+        cols = self.num_classes + 1
+        hist_out = None if buf is None else buf.hist
+        if self.loss == "samples":
+            hist = segment.row_histogram(self._rows_iota(B), slab, S, cols, self.ignore_label, out=hist_out)
+        else:
+            from .preprocessing.nearest import nearest_sample
+            rows = nearest_sample(pts, smp, counts=counts, sample_counts=scnt, out=None if buf is None else buf.rows)
+            hist = segment.row_histogram(rows, labels, S, cols, self.ignore_label, out=hist_out)
+        return smp, hist, scnt
+
+    def step_on_samples(self, samples: torch.Tensor, hist: torch.Tensor, train: bool = True) -> Tuple[float, float]:
+        """Forward (+ backward + Adam step when ``train``) on sampled points
+        ``[B, S, 3]`` and the rows' class histograms ``[B, S, C + 1]``."""
+        if train:
+            self.model.train()
+            pred = self.net(samples)
+            loss = point_loss(pred, hist)
+            self.opt.zero_grad(set_to_none=True)
+            loss.backward()
+            self.opt.step()
+        else:
+            self.model.eval()
+            with torch.no_grad():
+                pred = self.model(samples)
+                loss = point_loss(pred, hist)
+        return loss.item(), point_accuracy_tensor(pred.detach(), hist).item()
+
+    def step(self, points: torch.Tensor, gt_points: torch.Tensor, train: bool = True,
+             counts=None) -> Tuple[float, float]:
+        """One batch of whole scans: ``points`` [B,n,3], ``gt_points`` one-hot
+        [B,n,C+1] or integer class ids [B,n], ``counts`` the per-cloud point
+        counts of a ragged batch -> ``(loss, accuracy)``."""
+        if train and self.graphs:
+            loss, acc = self.step_graphed(points, gt_points, counts)
+            return loss.item(), acc.item()
+        smp, hist, _ = self.samples_and_targets(points, gt_points, counts, train=train)
+        return self.step_on_samples(smp, hist, train)
+
+    def _graph_for(self, points_shape, gt_shape, ragged: bool = False) -> "GraphedBaselineStep":
+        key = (tuple(points_shape), tuple(gt_shape)) + ((True,) if ragged else ())
+        g = self._graphed.get(key)
+        if g is None:
+            if self._graphed:  # one captured step per trainer: see the class docstring
+                have = next(iter(self._graphed))
+                raise ValueError(f"BaselineTrainer(graphs=True) captures one batch shape and has captured {have}; "
+                                 f"got {key}.  Pad the batches to one length (counts say where a cloud ends) and "
+                                 "keep one label form and the choice of counts, or use graphs=False")
+            gt_width = gt_shape[-1] if len(gt_shape) == 3 else None  # None: integer class ids
+            g = self._graphed[key] = GraphedBaselineStep(self, points_shape, gt_width, ragged=ragged)
+        return g
+
+    def step_graphed(self, points: torch.Tensor, gt_points: torch.Tensor,
+                     counts=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A training step as a graph replay; returns (loss, accuracy) as device
+        scalars, without synchronising (``Trainer.step_graphed``)."""
+        from .preprocessing.ndtnet_preprocessing import check_class_ids, check_counts
+        check_class_ids(gt_points, points)
+        if counts is not None:
+            check_counts(counts, points.shape[0], points.shape[1])
+        return self._graph_for(points.shape, gt_points.shape, counts is not None)(points, gt_points, counts)
+
+    def graph_inputs(self, points_shape, gt_shape, counts: bool = False):
+        """The static (points, gt[, counts]) buffers the captured step of this
+        shape reads (``Trainer.graph_inputs``)."""
+        g = self._graph_for(points_shape, gt_shape, bool(counts))
+        return (g.s_points, g.s_gt, g.s_counts) if counts else (g.s_points, g.s_gt)
+
+
+class GraphedBaselineStep:
+    """The baseline's training step for one input shape, captured once and
+    replayed, built like ``GraphedTrainStep``: static input buffers
+    (``s_points``, ``s_gt`` float one-hot or int32 ids, ``s_counts`` with
+    ``ragged=True``) and every sampler / rows / histogram buffer allocated
+    once; a few eager steps on a side stream first; parameters, buffers,
+    optimizer state, the sampler's counter and the augmentation's snapshotted
+    before them and restored after the capture, so the first replay is draw 0
+    of the trainer's first step and every replay draws anew."""
+
+    def __init__(self, trainer: BaselineTrainer, points_shape, gt_width: Optional[int], warmup: int = 3,
+                 ragged: bool = False) -> None:
+        tr = self.tr = trainer
+        dev = tr.device
+        B, n = int(points_shape[0]), int(points_shape[1])
+        if tr.n_samples > n:
+            raise ValueError(f"n_samples = {tr.n_samples} needs scans padded to at least that many points, got n = {n}")
+        self.s_points = torch.zeros((B, n, 3), dtype=torch.float32, device=dev)
+        if gt_width is None:  # integer class ids (class 0 for the warm-up steps)
+            self.s_gt = torch.zeros((B, n), dtype=torch.int32, device=dev)
+        else:
+            self.s_gt = torch.zeros((B, n, int(gt_width)), dtype=torch.float32, device=dev)
+            self.s_gt[..., 0] = 1.0
+        self.s_counts = torch.full((B,), n, dtype=torch.int32, device=dev) if ragged else None
+        self.buffers = _BaselineBuffers(B, n, tr.n_samples, tr.num_classes + 1, dev, tr.sampler, tr.loss)
+        gen = torch.Generator(device=dev).manual_seed(0)
+        self.s_points.copy_(torch.rand(self.s_points.shape, device=dev, generator=gen) * 20 - 10)
+        counters = [tr.random_sample.step_tensor(dev)]
+        if tr.augment is not None:
+            counters.append(tr.augment.step_tensor(dev))
+        self.graph, (self.loss, self.acc) = _capture_step(tr.model, tr.opt, dev, self._body, counters, warmup)
+
+    def _body(self):
+        tr = self.tr
+        smp, hist, _ = tr.samples_and_targets(self.s_points, self.s_gt, self.s_counts, train=True,
+                                              buffers=self.buffers)
+        tr.model.train()
+        pred = tr.net(smp)
+        loss = point_loss(pred, hist)
+        loss.backward()
+        tr.opt.step()
+        return loss.detach(), point_accuracy_tensor(pred.detach(), hist)
+
+    def __call__(self, points: torch.Tensor, gt_points: torch.Tensor,
+                 counts=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        return _replay_step(self, points, gt_points, counts)
